@@ -16,6 +16,12 @@ falls back to the round-1 subprocess-worker path.
 Synthetic workload: deterministic pipedream-format job graphs (the
 reference's "small_graphs" profile set is not distributed); random-init GNN
 weights.
+
+A plain run sets up, warms up, times --steps PPO iterations and prints one
+JSON result line.  --dump-outputs DIR also writes the last timed step's
+results as .npy files (same arguments -> same seeded inputs, so two builds
+compare output for output); --full is the home of any extra measurement that
+takes runs of its own.
 """
 import argparse
 import json
@@ -67,6 +73,40 @@ def build_env_fn(seed_offset: int = 0, device_type: str = "A100",
     return make
 
 
+# scalar stats of PPOTrainer.train() written to train_stats.npy, in this order
+# (NaN where the step did not report one)
+DUMP_STAT_KEYS = ("policy_loss", "vf_loss", "kl", "entropy", "total_loss",
+                  "kl_analytic", "kl_coeff", "mean_reward",
+                  "env_steps_this_iter", "total_env_steps")
+# per-sample arrays of the last step's train batch (PPOTrainer.collect_rollout)
+DUMP_BATCH_KEYS = ("actions", "logp", "values", "rewards", "advantages",
+                   "value_targets", "lp_all")
+
+
+def dump_outputs(out_dir, stats, batch, policy):
+    """Write what the last timed PPO step produced as <out_dir>/<name>.npy:
+    the stats train() returned, the policy weights it left behind and the
+    rollout batch it trained on.  float32/float64 only, a few hundred kB."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        arr = np.asarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+    save("train_stats", np.array([stats.get(k, np.nan) for k in DUMP_STAT_KEYS],
+                                 dtype=np.float64))
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float().cpu()
+                          for _, p in policy.named_parameters()])
+    save("policy_params", flat.numpy())
+    if batch is not None:
+        for k in DUMP_BATCH_KEYS:
+            if batch.get(k) is not None:
+                save("batch_" + k, batch[k])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -86,7 +126,17 @@ def main():
     ap.add_argument("--no-precompute", action="store_true",
                     help="(cpu-envs) skip the batched GPU lookahead memo "
                          "precompute")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "computed (train stats, policy weights, rollout "
+                         "batch) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements that need runs "
+                         "of their own (none yet: the plain run measures the "
+                         "headline figure only, and extras belong here)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from ddls_amd.models.gnn import GNNPolicy
     from ddls_amd.parallel import (get_world_size,
@@ -155,6 +205,17 @@ def main():
         if use_cuda:
             torch.cuda.synchronize()
 
+    last_batch = {}
+    if args.dump_outputs:
+        # keep a reference to the batch train() hands to update(), so the
+        # last step's rollout can be written out next to its results
+        update = trainer.update
+
+        def update_keeping_batch(batch):
+            last_batch["batch"] = batch
+            return update(batch)
+        trainer.update = update_keeping_batch
+
     for _ in range(args.warmup):
         trainer.train(num_steps=args.rollout_steps_per_env)
 
@@ -204,6 +265,10 @@ def main():
     total_env_steps = args.steps * per_step_env_steps * world_size
     value = total_env_steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, st, last_batch.get("batch"),
+                     trainer.policy)
 
     if rank == 0:
         print(json.dumps({

@@ -53,6 +53,29 @@ def build_extensions(verbose: bool = False):
     return _EXT
 
 
+def _load_prebuilt():
+    """Import the extension build_extensions() left in the build directory
+    when this process may read the tree but not write it (another user built
+    it): load() takes a lock file there even when nothing needs compiling.
+    Returns None when the tree is writable, nothing is built, or the built
+    library is older than a source (then load() reports the real problem)."""
+    from ..utils.debug import debug_build_flags, debug_enabled
+    if debug_enabled():
+        return None  # debug mode sets up the runtime in build_extensions()
+    name = "ddls_amd_kernels" + ("_debug" if debug_build_flags() else "")
+    lib = os.path.join(_BUILD_DIR, name + ".so")
+    if os.access(_BUILD_DIR, os.W_OK) or not os.path.isfile(lib):
+        return None
+    if any(os.path.getmtime(s) > os.path.getmtime(lib) for s in _SOURCES):
+        return None
+    import importlib.util
+    import torch  # noqa: F401  (the library links against torch)
+    spec = importlib.util.spec_from_file_location(name, lib)
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
+
+
 def get_extension(required: bool = False):
     """Return the compiled extension module (building it on first use)."""
     global _EXT, _EXT_ERR
@@ -61,7 +84,9 @@ def get_extension(required: bool = False):
     if _EXT_ERR is not None and not required:
         return None
     try:
-        build_extensions(verbose=False)
+        _EXT = _load_prebuilt()
+        if _EXT is None:
+            build_extensions(verbose=False)
     except Exception as e:  # build toolchain missing etc.
         _EXT_ERR = e
         if required:

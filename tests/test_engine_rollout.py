@@ -280,8 +280,11 @@ def test_bench_dp2_cpu_engine_rehearsal():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ)
+    # hide any GPU from the ranks: this rehearsal is the CPU path even on a
+    # GPU machine
     env.update({"DDLS_AMD_DIST_BACKEND": "gloo",
-                "MASTER_ADDR": "127.0.0.1"})
+                "MASTER_ADDR": "127.0.0.1",
+                "HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": ""})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29741", "bench.py", "--gpus", "2",
@@ -298,3 +301,82 @@ def test_bench_dp2_cpu_engine_rehearsal():
     assert rec["config"]["env_engine"] == "cpu_engine"
     assert rec["value"] > 0
     assert rec["config"]["mean_simulated_jct"] is not None
+
+
+def _run_bench_in_process(monkeypatch, capsys, argv):
+    """bench.main() on the CpuEngine path, returning its result record."""
+    import json
+    import sys
+
+    import bench
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    capsys.readouterr()
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines()
+             if l.startswith("{")]
+    assert len(lines) == 1, "stdout must hold exactly one JSON result line"
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_reproducible(tmp_path, monkeypatch, capsys):
+    """--dump-outputs writes the last timed step's results as float .npy
+    files, identical between two runs with the same arguments (same seeded
+    inputs), and --steps sets the number of timed steps."""
+    import os
+
+    import bench
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1",
+            "--envs-per-rank", "8", "--rollout-steps-per-env", "4",
+            "--num-sgd-iter", "2", "--sgd-minibatch-size", "16"]
+    recs, dumps = [], []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        recs.append(_run_bench_in_process(
+            monkeypatch, capsys, argv + ["--dump-outputs", str(out)]))
+        dumps.append({f: np.load(out / f) for f in sorted(os.listdir(out))})
+
+    for rec in recs:
+        assert rec["metric"] == "ppo_env_steps_per_sec"
+        assert rec["steps"] == 2 and rec["warmup"] == 1
+        assert rec["ms_per_step"] > 0
+        # value and ms_per_step describe the same timed window
+        np.testing.assert_allclose(
+            rec["value"], 2 * 8 * 4 / (2 * rec["ms_per_step"] / 1e3),
+            rtol=1e-9)
+
+    a, b = dumps
+    expected = {"train_stats.npy", "policy_params.npy"} | {
+        f"batch_{k}.npy" for k in bench.DUMP_BATCH_KEYS}
+    assert set(a) == set(b) == expected
+    total_bytes = 0
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.isfinite(a[name]).all(), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+        total_bytes += a[name].nbytes
+    assert total_bytes <= 64 * 2 ** 20
+    n = 8 * 4
+    assert a["train_stats.npy"].shape == (len(bench.DUMP_STAT_KEYS),)
+    assert a["batch_actions.npy"].shape == (n,)
+    assert a["batch_lp_all.npy"].shape == (n, 17)
+    from ddls_amd.models.gnn import GNNPolicy
+    n_params = sum(p.numel() for p in GNNPolicy(num_actions=17).parameters())
+    assert a["policy_params.npy"].shape == (n_params,)
+    # 3 iterations ran in all (1 warmup + 2 timed) and the dump is the last
+    stats = dict(zip(bench.DUMP_STAT_KEYS, a["train_stats.npy"]))
+    assert stats["env_steps_this_iter"] == n
+    assert stats["total_env_steps"] == 3 * n
+
+
+def test_bench_full_flag_keeps_result_line(monkeypatch, capsys):
+    """--full is accepted and the result line keeps its headline fields."""
+    rec = _run_bench_in_process(
+        monkeypatch, capsys,
+        ["--gpus", "1", "--steps", "1", "--warmup", "0", "--envs-per-rank",
+         "4", "--rollout-steps-per-env", "2", "--num-sgd-iter", "1",
+         "--sgd-minibatch-size", "8", "--full"])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype",
+                "ms_per_step"):
+        assert key in rec
+    assert rec["unit"] == "env_steps/s" and rec["higher_is_better"] is True

@@ -443,3 +443,37 @@ def test_fused_policy_head_matches_eager():
     for n in g_e:
         assert torch.allclose(g_e[n], g_f[n], rtol=1e-3, atol=2e-4), \
             (n, (g_e[n] - g_f[n]).abs().max().item())
+
+
+def test_prebuilt_extension_loads_from_read_only_tree(monkeypatch):
+    """A process that may read the tree but not write it (another user ran
+    the build) must get the already-built extension without going through
+    the JIT loader, which takes a lock file in the build directory."""
+    import os
+
+    import torch.utils.cpp_extension as cpp_ext
+
+    from ddls_amd import ops
+    built = ops.get_extension(required=True)   # builds on first use
+
+    def no_jit(*a, **k):
+        raise PermissionError("read-only build directory")
+    real_access = os.access
+    monkeypatch.setattr(cpp_ext, "load", no_jit)
+    monkeypatch.setattr(
+        os, "access", lambda path, mode, **k: False
+        if (path == ops._BUILD_DIR and mode == os.W_OK)
+        else real_access(path, mode, **k))
+    monkeypatch.setattr(ops, "_EXT", None)
+    monkeypatch.setattr(ops, "_EXT_ERR", None)
+    ext = ops.get_extension(required=True)
+    assert ext is not None
+    assert sorted(n for n in dir(ext) if not n.startswith("_")) == \
+        sorted(n for n in dir(built) if not n.startswith("_"))
+
+    # a library older than a source is not trusted: the loader is asked
+    monkeypatch.setattr(ops, "_EXT", None)
+    monkeypatch.setattr(os.path, "getmtime",
+                        lambda p: 0.0 if p.endswith(".so") else 1.0)
+    with pytest.raises(RuntimeError):
+        ops.get_extension(required=True)

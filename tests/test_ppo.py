@@ -95,6 +95,8 @@ def test_dp_all_reduce_gloo(tmp_path):
     env["DDLS_REPO"] = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env["MASTER_ADDR"] = "127.0.0.1"
     env["MASTER_PORT"] = "29617"
+    # CPU tensors: gloo also where a GPU would make RCCL the default backend
+    env["DDLS_AMD_DIST_BACKEND"] = "gloo"
     procs = []
     for rank in range(2):
         e = dict(env, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank))
