@@ -33,6 +33,19 @@
 
 #define LN_EPS 1e-5f
 
+// Gradients from this file are compared bitwise from one revision to the
+// next.  Whether the compiler contracts a*b+c into one fused multiply-add or
+// rounds the product first depends on its unrolling and packing choices, so
+// kernels that were restructured after such a comparison was first taken
+// spell out the rounding their predecessor had: FMA() is one rounding,
+// x + mul_rn(a, b) is two.
+#define FMA(a, b, c) __builtin_fmaf((a), (b), (c))
+__device__ __forceinline__ float mul_rn(float a, float b) {
+  float p = a * b;
+  asm("" : "+v"(p));   // opaque to the optimiser: stays a rounded product
+  return p;
+}
+
 // Compile-time dims of the tuned PAC-ML policy (model/gnn.yaml values).
 // fill_ptrs TORCH_CHECKs the runtime tensors against these; the Python side
 // (graph_step._FusedCachedEngine.eligible) refuses other shapes.  Constant
@@ -367,12 +380,34 @@ __global__ void __launch_bounds__(512)
 cs_fwd_pool_kernel(CachedPtrs P, CachedDims D) {
   const int tid = threadIdx.x;
   const int NT = blockDim.x;
-  for (long u = tid; u < (long)D.M * KOUT; u += NT) {
-    int m = (int)(u / KOUT), i = (int)(u % KOUT);
-    long lo = P.model_nptr[m], hi = P.model_nptr[m + 1];
+  constexpr int PT = 256;   // node rows of h2 staged per tile
+  __shared__ float sH2[PT * KOUT];
+  __shared__ float sGam[KGF], sBet[KGF], sWg[KGE * KGF], sBg[KGE];
+  for (int i = tid; i < KGF; i += NT) {
+    sGam[i] = WP(W_LN_G_W)[i];
+    sBet[i] = WP(W_LN_G_B)[i];
+  }
+  for (int x = tid; x < KGE * KGF; x += NT) sWg[x] = WP(W_G_W)[x];
+  for (int o = tid; o < KGE; o += NT) sBg[o] = WP(W_G_B)[o];
+  // per-model means: h2 goes through LDS tile by tile; each (m, i) unit
+  // adds its model's nodes in node order, as a chain out of LDS
+  const int units = D.M * KOUT;
+  for (int ub = 0; ub < units; ub += NT) {
+    const int u = ub + tid;
+    const int m = u / KOUT, i = u % KOUT;
+    long lo = 0, hi = 0;
+    if (u < units) { lo = P.model_nptr[m]; hi = P.model_nptr[m + 1]; }
     float acc = 0.f;
-    for (long v = lo; v < hi; ++v) acc += P.h2[v * KOUT + i];
-    P.pooled[(long)m * KOUT + i] = acc / (float)(hi - lo);
+    for (long v0 = 0; v0 < D.N; v0 += PT) {
+      const long v1 = min((long)D.N, v0 + PT);
+      __syncthreads();
+      for (long x = tid; x < (v1 - v0) * KOUT; x += NT)
+        sH2[x] = P.h2[v0 * KOUT + x];
+      __syncthreads();
+      const long a = max(lo, v0), e = min(hi, v1);
+      for (long v = a; v < e; ++v) acc += sH2[(v - v0) * KOUT + i];
+    }
+    if (u < units) P.pooled[(long)m * KOUT + i] = acc / (float)(hi - lo);
   }
   __syncthreads();
   for (int b = tid; b < D.B; b += NT) {
@@ -382,14 +417,16 @@ cs_fwd_pool_kernel(CachedPtrs P, CachedDims D) {
     for (int i = 0; i < KOUT; ++i) fin[i] = P.pooled[mid * KOUT + i];
     float xh[KGF];
     ln_row_reg<KGF>(P.gf + (long)b * KGF, xh, P.xh34 + (long)b * KGF);
-    const float* __restrict__ gam = WP(W_LN_G_W);
-    const float* __restrict__ bet = WP(W_LN_G_B);
-    const float* __restrict__ Wg = WP(W_G_W);
-    const float* __restrict__ bg = WP(W_G_B);
+    const float* __restrict__ gam = sGam;
+    const float* __restrict__ bet = sBet;
+    const float* __restrict__ Wg = sWg;
+    const float* __restrict__ bg = sBg;
     float uu[KGF];
 #pragma unroll
     for (int i = 0; i < KGF; ++i) uu[i] = xh[i] * gam[i] + bet[i];
-#pragma unroll
+    // not unrolled over o: with the weights in LDS a full unroll hoists all
+    // KGE*KGF reads and spills
+#pragma unroll 1
     for (int o = 0; o < KGE; ++o) {
       float acc = bg[o];
 #pragma unroll
@@ -539,6 +576,10 @@ __global__ void __launch_bounds__(256)
 cs_bwd_head_kernel(CachedPtrs P, CachedDims D) {
   __shared__ float sW2p[KA * KFC], sW2v[KFC];
   __shared__ float sW1p[KFC * KFIN], sW1v[KFC * KFIN], sWg[KGE * KGF];
+  constexpr int HS = 4;   // samples in flight per block
+  // per-sample rows; +1 keeps the HS rows of one column on distinct banks
+  __shared__ float sGL[HS][KA], sGV[HS], sGF[HS][KFIN];
+  __shared__ float sGHp[HS][KFC + 1], sGHv[HS][KFC + 1];
   const int tid = threadIdx.x;
   const int NT = blockDim.x;
   for (int x = tid; x < KA * KFC; x += NT) sW2p[x] = WP(W_P2_W)[x];
@@ -552,55 +593,81 @@ cs_bwd_head_kernel(CachedPtrs P, CachedDims D) {
   const int per = (D.B + gridDim.x - 1) / gridDim.x;
   const int b0 = blockIdx.x * per;
   const int b1 = min(D.B, b0 + per);
-  for (int b = b0; b < b1; ++b) {
-    // loss backward row (upstream grad = 1)
-    for (int a = tid; a < KA; a += NT) {
+  // HS samples go through the phases side by side; each sample's rows stay
+  // in LDS between phases (they are also written out for cs_bwd_w), so no
+  // phase waits on a global store -> load round trip.
+  for (int c0 = b0; c0 < b1; c0 += HS) {
+    const int ns = min(HS, b1 - c0);
+    // loss backward rows (upstream grad = 1)
+    for (int x = tid; x < ns * KA; x += NT) {
+      const int s = x / KA, a = x % KA;
+      const int b = c0 + s;
       const long u = (long)b * KA + a;
       const long act = P.actions[b];
       const float c = P.coef[b] / D.B;
       const float pj = P.p[u];
       const float lpj = P.lp[u];
       const float delta = (a == (int)act) ? 1.f : 0.f;
-      P.glogits[u] = c * (delta - pj)
-                     + (D.ent_coef / D.B) * pj * (lpj + P.hent[b]);
+      const float gl = mul_rn(c, delta - pj)
+                       + mul_rn(mul_rn(D.ent_coef / D.B, pj),
+                                lpj + P.hent[b]);
+      P.glogits[u] = gl;
+      sGL[s][a] = gl;
     }
-    if (tid == 0) {
+    if (tid >= 128 && tid < 128 + ns) {
+      const int s = tid - 128;
+      const int b = c0 + s;
       const float verr = P.values[b] - P.vtarg[b];
       const float mk = (verr * verr <= D.vf_clip) ? 1.f : 0.f;
-      P.gvalue[b] = D.vf_coef * 2.f * verr * mk / D.B;
+      const float gv = D.vf_coef * 2.f * verr * mk / D.B;
+      P.gvalue[b] = gv;
+      sGV[s] = gv;
     }
     __syncthreads();
     // hidden grads
-    for (int j = tid; j < KFC; j += NT) {
-      const long u = (long)b * KFC + j;
+    for (int x = tid; x < ns * KFC; x += NT) {
+      const int s = x / KFC, j = x % KFC;
+      const long u = (long)(c0 + s) * KFC + j;
       float acc = 0.f;
 #pragma unroll
-      for (int a = 0; a < KA; ++a)
-        acc += sW2p[a * KFC + j] * P.glogits[(long)b * KA + a];
-      P.gh1p[u] = P.h1p[u] > 0.f ? acc : 0.f;
-      const float av = sW2v[j] * P.gvalue[b];
-      P.gh1v[u] = P.h1v[u] > 0.f ? av : 0.f;
+      for (int a = 0; a < KA; ++a) {
+        // the first five terms are fused, the rest rounded products
+        if (a < 5) acc = FMA(sW2p[a * KFC + j], sGL[s][a], acc);
+        else acc = acc + mul_rn(sW2p[a * KFC + j], sGL[s][a]);
+      }
+      const float gp = P.h1p[u] > 0.f ? acc : 0.f;
+      const float av = sW2v[j] * sGV[s];
+      const float gv = P.h1v[u] > 0.f ? av : 0.f;
+      P.gh1p[u] = gp;
+      P.gh1v[u] = gv;
+      sGHp[s][j] = gp;
+      sGHv[s][j] = gv;
     }
     __syncthreads();
-    // gfinal + graph-module LN-out grads
-    for (int i = tid; i < KFIN; i += NT) {
+    // gfinal: one thread per (sample, i), j = 0..FC-1 in order
+    for (int x = tid; x < ns * KFIN; x += NT) {
+      const int s = x / KFIN, i = x % KFIN;
       float acc = 0.f;
 #pragma unroll 8
       for (int j = 0; j < KFC; ++j) {
-        acc += sW1p[j * KFIN + i] * P.gh1p[(long)b * KFC + j];
-        acc += sW1v[j * KFIN + i] * P.gh1v[(long)b * KFC + j];
+        acc = FMA(sW1p[j * KFIN + i], sGHp[s][j], acc);
+        acc = FMA(sW1v[j * KFIN + i], sGHv[s][j], acc);
       }
-      P.gfinal[(long)b * KFIN + i] = acc;
+      P.gfinal[(long)(c0 + s) * KFIN + i] = acc;
+      sGF[s][i] = acc;
     }
     __syncthreads();
-    for (int i = tid; i < KGF; i += NT) {
+    // graph-module LN-out grads
+    for (int x = tid; x < ns * KGF; x += NT) {
+      const int s = x / KGF, i = x % KGF;
       float acc = 0.f;
 #pragma unroll
       for (int o = 0; o < KGE; ++o)
-        acc += sWg[o * KGF + i] * P.gfinal[(long)b * KFIN + KOUT + o];
-      P.gu34[(long)b * KGF + i] = acc;
+        acc = acc + mul_rn(sWg[o * KGF + i], sGF[s][KOUT + o]);
+      P.gu34[(long)(c0 + s) * KGF + i] = acc;
     }
-    __syncthreads();
+    // no barrier here: every row buffer's next write is at least one
+    // barrier after its last read above
   }
 }
 
@@ -612,13 +679,32 @@ cs_bwd_pool_kernel(CachedPtrs P, CachedDims D) {
   __shared__ int smid[1024];
   for (int b = tid; b < D.B; b += NT) smid[b] = (int)P.model_ids[b];
   __syncthreads();
-  for (long u = tid; u < (long)D.M * KOUT; u += NT) {
-    int m = (int)(u / KOUT), i = (int)(u % KOUT);
+  // gfinal[:, :KOUT] goes through LDS in tiles of BT samples; each (m, i)
+  // unit still adds b = 0..B-1 in order
+  constexpr int BT = 128;
+  __shared__ float sG[BT][KOUT];
+  const int units = D.M * KOUT;
+  for (int ub = 0; ub < units; ub += NT) {
+    const int u = ub + tid;
+    const int m = u / KOUT, i = u % KOUT;
     float acc = 0.f;
+    for (int t0 = 0; t0 < D.B; t0 += BT) {
+      const int bt = min(BT, D.B - t0);
+      __syncthreads();
+      for (int x = tid; x < bt * KOUT; x += NT)
+        sG[x / KOUT][x % KOUT] = P.gfinal[(long)(t0 + x / KOUT) * KFIN
+                                          + x % KOUT];
+      __syncthreads();
+      if (bt == BT) {
 #pragma unroll 8
-    for (int b = 0; b < D.B; ++b)
-      acc += (smid[b] == m) ? P.gfinal[(long)b * KFIN + i] : 0.f;
-    P.gpool[u] = acc;
+        for (int b = 0; b < BT; ++b)
+          acc += (smid[t0 + b] == m) ? sG[b][i] : 0.f;
+      } else {
+        for (int b = 0; b < bt; ++b)
+          acc += (smid[t0 + b] == m) ? sG[b][i] : 0.f;
+      }
+    }
+    if (u < units) P.gpool[u] = acc;
   }
   __syncthreads();
   for (long u = tid; u < (long)D.N * KOUT; u += NT) {
@@ -899,61 +985,6 @@ __device__ __forceinline__ void wgrad_tiled(
   }
 }
 
-template <int Din, int Dout>
-__device__ __forceinline__ void wgrad_plain(
-    const CachedPtrs& P, int tid, int NT, int rows,
-    const float* __restrict__ g, int g_stride,
-    const float* __restrict__ u, int u_stride,
-    int w_off_w, int w_off_b, float* lds) {
-  float* tG = lds;                       // [TILE_K][Dout]
-  float* tU = lds + TILE_K * Dout;       // [TILE_K][Din]
-  constexpr int UNITS = Din * Dout;
-  constexpr int MYU = (UNITS + 255) / 256;
-  float acc[MYU];
-#pragma unroll
-  for (int q = 0; q < MYU; ++q) acc[q] = 0.f;
-  float bacc = 0.f;
-  for (int r0 = 0; r0 < rows; r0 += TILE_K) {
-    const int rt = min(TILE_K, rows - r0);
-    for (int x = tid; x < rt * Dout; x += NT) {
-      int t = x / Dout, o = x % Dout;
-      tG[t * Dout + o] = g[(long)(r0 + t) * g_stride + o];
-    }
-    for (int x = tid; x < rt * Din; x += NT) {
-      int t = x / Din, i = x % Din;
-      tU[t * Din + i] = u[(long)(r0 + t) * u_stride + i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < MYU; ++q) {
-      int uu = tid + q * 256;
-      if (uu < UNITS) {
-        int o = uu / Din, i = uu % Din;
-        float a = acc[q];
-        if (rt == TILE_K) {
-#pragma unroll
-          for (int t = 0; t < TILE_K; ++t)
-            a += tG[t * Dout + o] * tU[t * Din + i];
-        } else {
-          for (int t = 0; t < rt; ++t)
-            a += tG[t * Dout + o] * tU[t * Din + i];
-        }
-        acc[q] = a;
-      }
-    }
-    if (tid < Dout)
-      for (int t = 0; t < rt; ++t) bacc += tG[t * Dout + tid];
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < MYU; ++q) {
-    int uu = tid + q * 256;
-    if (uu < UNITS) (P.flat_g + w_off_w)[uu] = acc[q];
-  }
-  if (tid < Dout) (P.flat_g + w_off_b)[tid] = bacc;
-}
-
-
 // ---------------------------------------------------------------------------
 // MFMA weight-grad contraction: gW[Dout,Din] = sum_r gpre[r,:] (x) u[r,:]
 // on v_mfma_f32_16x16x4_f32 tiles (exact f32: the result is a k-ordered fmaf
@@ -1145,70 +1176,90 @@ cs_bwd_w_kernel(CachedPtrs P, CachedDims D) {
   }
 
   // ---- special jobs over the B sample rows ----
+  // Rule for all of them: operands are staged into LDS tile by tile with
+  // coalesced cooperative loads, then every output element is reduced in
+  // the original b = 0..B-1 order (tile by tile, t within the tile) — a
+  // serial chain out of LDS, never a chain of dependent global loads.
   if ((int)blockIdx.x == jobs_end) {
-    // graph module: Wg[GEMB,GFin], bg; LN gamma/beta from gu34 + xh34
-    const float* gam = WP(W_LN_G_W);
-    const float* bet = WP(W_LN_G_B);
-    const int units = KGE * KGF;
-    for (int u = tid; u < units; u += NT) {
-      int o = u / KGF, i = u % KGF;
-      float a = 0.f;
-      for (int b = 0; b < D.B; ++b)
-        a += P.gfinal[(long)b * KFIN + KOUT + o]
-             * (P.xh34[(long)b * KGF + i] * gam[i] + bet[i]);
-      WG_(W_G_W)[u] = a;
-    }
-    for (int o = tid; o < KGE; o += NT) {
-      float a = 0.f;
-      for (int b = 0; b < D.B; ++b)
-        a += P.gfinal[(long)b * KFIN + KOUT + o];
-      WG_(W_G_B)[o] = a;
-    }
-    for (int i = tid; i < KGF; i += NT) {
-      float gw = 0.f, gb = 0.f;
-      for (int b = 0; b < D.B; ++b) {
-        const float gu = P.gu34[(long)b * KGF + i];
-        gw += gu * P.xh34[(long)b * KGF + i];
-        gb += gu;
+    // graph module: Wg[GEMB,GFin], bg; LN gamma/beta from gu34 + xh34.
+    // gpre rows are gfinal[:, KOUT:KOUT+KGE] (row stride KFIN).
+    const float* __restrict__ gam = WP(W_LN_G_W);
+    const float* __restrict__ bet = WP(W_LN_G_B);
+    constexpr int UNITS = KGE * KGF;
+    constexpr int MYU = (UNITS + 255) / 256;
+    float acc[MYU];
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) acc[q] = 0.f;
+    // tid in [64, 64+KGE): bias sums; tid in [128, 128+KGF): LN gamma/beta
+    float bacc = 0.f, lacc_w = 0.f, lacc_b = 0.f;
+    for (int r0 = 0; r0 < D.B; r0 += TILE_K) {
+      const int rt = min(TILE_K, D.B - r0);
+      for (int x = tid; x < rt * KGE; x += NT) {
+        int t = x / KGE, o = x % KGE;
+        tG[t][o] = P.gfinal[(long)(r0 + t) * KFIN + KOUT + o];
       }
-      WG_(W_LN_G_W)[i] = gw;
-      WG_(W_LN_G_B)[i] = gb;
+      for (int x = tid; x < rt * KGF; x += NT) {
+        int t = x / KGF, i = x % KGF;
+        const float xh = P.xh34[(long)r0 * KGF + x];
+        tU[t][i] = FMA(xh, gam[i], bet[i]);
+        tXH[t][i] = xh;
+        tGU[t][i] = P.gu34[(long)r0 * KGF + x];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < MYU; ++q) {
+        int u = tid + q * 256;
+        if (u < UNITS) {
+          int o = u / KGF, i = u % KGF;
+          float a = acc[q];
+          for (int t = 0; t < rt; ++t) a = FMA(tG[t][o], tU[t][i], a);
+          acc[q] = a;
+        }
+      }
+      if (tid >= 64 && tid < 64 + KGE)
+        for (int t = 0; t < rt; ++t) bacc += tG[t][tid - 64];
+      if (tid >= 128 && tid < 128 + KGF)
+        for (int t = 0; t < rt; ++t) {
+          lacc_w = lacc_w + mul_rn(tGU[t][tid - 128], tXH[t][tid - 128]);
+          lacc_b += tGU[t][tid - 128];
+        }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) {
+      int u = tid + q * 256;
+      if (u < UNITS) WG_(W_G_W)[u] = acc[q];
+    }
+    if (tid >= 64 && tid < 64 + KGE) WG_(W_G_B)[tid - 64] = bacc;
+    if (tid >= 128 && tid < 128 + KGF) {
+      WG_(W_LN_G_W)[tid - 128] = lacc_w;
+      WG_(W_LN_G_B)[tid - 128] = lacc_b;
     }
     return;
   }
-  if ((int)blockIdx.x == jobs_end + 1) {
-    // W2p[A,FC] = sum_b glogits (x) h1p (LDS-tiled); b2p folded in
-    __shared__ float lbuf[TILE_K * (KA + KFC)];
-    wgrad_plain<KFC, KA>(P, tid, NT, D.B, P.glogits, KA, P.h1p, KFC,
-                         (int)P.offs[W_P2_W], (int)P.offs[W_P2_B], lbuf);
-    __syncthreads();
-    for (int j = tid; j < KFC; j += NT) {
-      float acc = 0.f;
-      for (int b = 0; b < D.B; ++b)
-        acc += P.gvalue[b] * P.h1v[(long)b * KFC + j];
-      WG_(W_V2_W)[j] = acc;
-    }
-    if (tid == 0) {
-      float acc = 0.f;
-      for (int b = 0; b < D.B; ++b) acc += P.gvalue[b];
-      WG_(W_V2_B)[0] = acc;
-    }
-    return;
-  }
-  // remaining blocks: W1p/W1v [FC,FIN] split FC-rows across blocks; LDS
-  // tiles of fin AND the gh1p/gh1v column slices
+  // remaining blocks split the FC columns: block jb owns columns [j0, j1)
+  // of W1p/W1v [FC,FIN] (+ b1p/b1v) AND of W2p [A,FC] / W2v [FC]; block 0
+  // also sums b2p and b2v.
   {
-    const int nb = gridDim.x - jobs_end - 2;
-    const int jb = blockIdx.x - jobs_end - 2;
+    const int nb = gridDim.x - jobs_end - 1;
+    const int jb = blockIdx.x - jobs_end - 1;
     const int per = (KFC + nb - 1) / nb;
     const int j0 = jb * per, j1 = min(KFC, j0 + per);
     const int JW = j1 - j0;
     __shared__ float tF[TILE_K][KFIN];
     __shared__ float tGp[TILE_K][16], tGv[TILE_K][16];
+    __shared__ float tHp[TILE_K][16], tHv[TILE_K][16];
+    __shared__ float tGL[TILE_K][KA], tGV[TILE_K];
     constexpr int MYU = (16 * KFIN + 255) / 256;   // JW <= 16
-    float accp[MYU], accv[MYU];
+    constexpr int MYU2 = (16 * KA + 255) / 256;
+    float accp[MYU], accv[MYU], acc2[MYU2];
 #pragma unroll
     for (int q = 0; q < MYU; ++q) { accp[q] = 0.f; accv[q] = 0.f; }
+#pragma unroll
+    for (int q = 0; q < MYU2; ++q) acc2[q] = 0.f;
+    // tid < JW: column sums b1p/b1v and the W2v column; jb == 0 only:
+    // tid in [64, 64+KA) sums b2p, tid == 128 sums b2v
+    float bp = 0.f, bv = 0.f, w2v = 0.f, b2 = 0.f;
     for (int r0 = 0; r0 < D.B; r0 += TILE_K) {
       const int rt = min(TILE_K, D.B - r0);
       for (int x = tid; x < rt * KFIN; x += NT) {
@@ -1217,9 +1268,15 @@ cs_bwd_w_kernel(CachedPtrs P, CachedDims D) {
       }
       for (int x = tid; x < rt * JW; x += NT) {
         int t = x / JW, j = x % JW;
-        tGp[t][j] = P.gh1p[(long)(r0 + t) * KFC + j0 + j];
-        tGv[t][j] = P.gh1v[(long)(r0 + t) * KFC + j0 + j];
+        const long g = (long)(r0 + t) * KFC + j0 + j;
+        tGp[t][j] = P.gh1p[g];
+        tGv[t][j] = P.gh1v[g];
+        tHp[t][j] = P.h1p[g];
+        tHv[t][j] = P.h1v[g];
       }
+      for (int x = tid; x < rt * KA; x += NT)
+        tGL[x / KA][x % KA] = P.glogits[(long)r0 * KA + x];
+      for (int t = tid; t < rt; t += NT) tGV[t] = P.gvalue[r0 + t];
       __syncthreads();
 #pragma unroll
       for (int q = 0; q < MYU; ++q) {
@@ -1230,18 +1287,51 @@ cs_bwd_w_kernel(CachedPtrs P, CachedDims D) {
           if (rt == TILE_K) {
 #pragma unroll
             for (int t = 0; t < TILE_K; ++t) {
-              ap += tGp[t][j] * tF[t][i];
-              av += tGv[t][j] * tF[t][i];
+              ap = FMA(tGp[t][j], tF[t][i], ap);
+              av = FMA(tGv[t][j], tF[t][i], av);
             }
           } else {
             for (int t = 0; t < rt; ++t) {
-              ap += tGp[t][j] * tF[t][i];
-              av += tGv[t][j] * tF[t][i];
+              ap = FMA(tGp[t][j], tF[t][i], ap);
+              av = FMA(tGv[t][j], tF[t][i], av);
             }
           }
           accp[q] = ap;
           accv[q] = av;
         }
+      }
+#pragma unroll
+      for (int q = 0; q < MYU2; ++q) {
+        int u = tid + q * NT;
+        if (u < KA * JW) {
+          int a = u / JW, j = u % JW;
+          float s = acc2[q];
+          if (rt == TILE_K) {
+#pragma unroll
+            for (int t = 0; t < TILE_K; ++t) {
+              // a full tile's first 20 terms are fused, the last 12 are
+              // rounded products; a partial tile is fused throughout
+              if (t < 20) s = FMA(tGL[t][a], tHp[t][j], s);
+              else s = s + mul_rn(tGL[t][a], tHp[t][j]);
+            }
+          } else {
+            for (int t = 0; t < rt; ++t) s = FMA(tGL[t][a], tHp[t][j], s);
+          }
+          acc2[q] = s;
+        }
+      }
+      if (tid < JW) {
+        for (int t = 0; t < rt; ++t) {
+          bp += tGp[t][tid];
+          bv += tGv[t][tid];
+          w2v = FMA(tGV[t], tHv[t][tid], w2v);
+        }
+      }
+      if (jb == 0) {
+        if (tid >= 64 && tid < 64 + KA)
+          for (int t = 0; t < rt; ++t) b2 += tGL[t][tid - 64];
+        if (tid == 128)
+          for (int t = 0; t < rt; ++t) b2 += tGV[t];
       }
       __syncthreads();
     }
@@ -1254,14 +1344,22 @@ cs_bwd_w_kernel(CachedPtrs P, CachedDims D) {
         WG_(W_V1_W)[(long)(j0 + j) * KFIN + i] = accv[q];
       }
     }
-    for (int j = j0 + tid; j < j1; j += NT) {
-      float ap = 0.f, av = 0.f;
-      for (int b = 0; b < D.B; ++b) {
-        ap += P.gh1p[(long)b * KFC + j];
-        av += P.gh1v[(long)b * KFC + j];
+#pragma unroll
+    for (int q = 0; q < MYU2; ++q) {
+      int u = tid + q * NT;
+      if (u < KA * JW) {
+        int a = u / JW, j = u % JW;
+        WG_(W_P2_W)[(long)a * KFC + j0 + j] = acc2[q];
       }
-      WG_(W_P1_B)[j] = ap;
-      WG_(W_V1_B)[j] = av;
+    }
+    if (tid < JW) {
+      WG_(W_P1_B)[j0 + tid] = bp;
+      WG_(W_V1_B)[j0 + tid] = bv;
+      WG_(W_V2_W)[j0 + tid] = w2v;
+    }
+    if (jb == 0) {
+      if (tid >= 64 && tid < 64 + KA) WG_(W_P2_B)[tid - 64] = b2;
+      if (tid == 128) WG_(W_V2_B)[0] = b2;
     }
   }
 }
@@ -1470,6 +1568,8 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
   CachedDims D;
   fill_ptrs(P, D, T, fs);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  // cs_bwd_pool keeps the minibatch's model ids in a fixed LDS array
+  TORCH_CHECK(D.B <= 1024, "cached_step: minibatch larger than 1024");
   int hb = D.B < 32 ? D.B : 32;
   const int rows_b = (D.N + D.E + 255) / 256;
   const int scat_b = ((long)(D.N + D.E) * D.H + 255) / 256;
@@ -1490,7 +1590,8 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
   hipLaunchKernelGGL(cs_bwd_gu1_kernel, dim3(rows_b), dim3(256), 0, stream,
                      P, D);
   const int nsplit = D.wgrad_mfma ? 1 : WSPLIT;
-  hipLaunchKernelGGL(cs_bwd_w_kernel, dim3(6 * nsplit + 2 + 16), dim3(256),
+  // 6 row jobs x nsplit, the graph-module block, 16 FC-column blocks
+  hipLaunchKernelGGL(cs_bwd_w_kernel, dim3(6 * nsplit + 1 + 16), dim3(256),
                      0, stream, P, D);
   if (nsplit > 1)
     hipLaunchKernelGGL(cs_bwd_w_reduce_kernel, dim3(6), dim3(256), 0,
