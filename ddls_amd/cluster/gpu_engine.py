@@ -45,12 +45,24 @@ def _pack_spec_tensors(spec: EngineSpec, device) -> Dict[str, torch.Tensor]:
     md_pjseq = np.zeros(max(D, 1))
     md_degree = np.zeros(max(D, 1), dtype=np.int32)
     md_model = np.zeros(max(D, 1), dtype=np.int32)
+    # throughput-reward quantity each running job contributes per tick: the
+    # SAME Python f64 expressions cpu_step_env evaluates, so the kernel reads
+    # the already-rounded sum (all zeros for the non-throughput rewards)
+    md_tpq = np.zeros(max(D, 1))
+    tp_kind = int(spec.reward.tp_kind)
     for d, md in enumerate(spec.mds):
         seq_len = spec.models[md.model_id].seq_len
         md_splits[d, :seq_len] = md.splits
         md_pjseq[d] = md.pj_seq
         md_degree[d] = md.degree
         md_model[d] = md.model_id
+        if tp_kind == 1:
+            md_tpq[d] = md.pj_mem
+        elif tp_kind == 2:
+            md_tpq[d] = md.pj_mem + md.pj_dep
+        elif tp_kind == 3:
+            ms = spec.models[md.model_id]
+            md_tpq[d] = ms.mem_total + ms.dep_total
 
     t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), device=device,
                                       dtype=dt)
@@ -69,6 +81,7 @@ def _pack_spec_tensors(spec: EngineSpec, device) -> Dict[str, torch.Tensor]:
         "md_pjseq": t(md_pjseq, torch.float64),
         "md_degree": t(md_degree, torch.int32),
         "md_model": t(md_model, torch.int32),
+        "md_tpq": t(md_tpq, torch.float64),
         "_SEQ_CAP": SEQ_CAP, "_PAR_CAP": max(PAR_CAP, 1),
     }
 
@@ -183,6 +196,8 @@ class GpuEngine:
             "obs_mask": z((B, A), torch.float32),
             "reward": z((B,), torch.float64),
             "step_done": z((B,), torch.uint8),
+            "tp_info": z((B,), torch.float64),
+            "tp_time": z((B,), torch.float64),
             "actions": z((B,), torch.int32),
         })
         self._state_alloc_done = True
@@ -221,6 +236,8 @@ class GpuEngine:
         T["snapshot"][b] = 0
         T["ep_return"][b] = 0.0
         T["ep_len"][b] = 0
+        T["tp_info"][b] = 0.0
+        T["tp_time"][b] = 0.0
         T["done"][b] = 0
         T["status"][b] = 0
         T["log_status"][b] = PENDING
@@ -238,7 +255,7 @@ class GpuEngine:
     # ------------------------------------------------------------------
     _ORDER = ("static_ok", "shape_ptr", "shapes", "model_gf", "model_seq",
               "model_a2md", "model_seq_len", "op_mem", "par_ptr", "par_idx",
-              "md_splits", "md_pjseq", "md_degree", "md_model",
+              "md_splits", "md_pjseq", "md_degree", "md_model", "md_tpq",
               "hash_keys", "hash_vals",
               "sch_model", "sch_frac", "sch_acc", "sch_nominal", "sch_n",
               "sch_params",
@@ -247,20 +264,16 @@ class GpuEngine:
               "occ", "snapshot", "ep_return", "ep_len", "done", "status",
               "log_status", "log_md", "log_t_arr", "log_t_end", "log_order",
               "order_counter", "obs_model", "obs_sched", "obs_gf", "obs_mask",
-              "reward", "step_done", "actions")
+              "reward", "step_done", "tp_info", "tp_time", "actions")
 
     def _scalars(self):
         spec = self.spec
         r = spec.reward
-        if getattr(r, "tp_kind", 0):
-            raise ValueError(
-                "GpuEngine: throughput rewards are CPU-mirror-only for now "
-                "(env_step.hip port pending) — use the CPU env path")
         iscal = [self.B, spec.C, spec.R, spec.S, spec.W, self.WW, spec.A,
                  self.K, self.T["_SEQ_CAP"], self.T["_PAR_CAP"], self.SCH,
                  self.NJOBS, self.HS, int(spec.infinite_pool),
                  int(r.inverse), int(r.transform_with_log), int(r.normaliser),
-                 int(r.fail_const is None)]
+                 int(r.fail_const is None), int(r.tp_kind)]
         fscal = [spec.eps, spec.max_sim, spec.mem_capacity, r.sign,
                  r.fail_factor,
                  0.0 if r.fail_const is None else r.fail_const,

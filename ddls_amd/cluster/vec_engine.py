@@ -123,7 +123,8 @@ class RewardSpec:
     # dep size), 3 demand_total (ORIGINAL job's totals).  Reward = the
     # first cluster step's info_processed / step_time (the RL env extracts
     # the reward right after cluster.step(action), before fast-forward).
-    # CPU-mirror support; the GPU kernel port is pending (GpuEngine gates).
+    # Accrued by both the CPU mirror and env_step.hip (bitwise-equal); the
+    # per-step numerator/denominator are kept in tp_info / tp_time.
     tp_kind: int = 0
 
 
@@ -615,6 +616,10 @@ class EngineState:
         # per-step outputs
         self.reward = np.zeros(B)
         self.step_done = np.zeros(B, dtype=bool)
+        # throughput-reward diagnostics of the last step: info processed and
+        # the step time it was divided by (both 0 for the other rewards)
+        self.tp_info = np.zeros(B)
+        self.tp_time = np.zeros(B)
 
     def reset_env(self, spec: EngineSpec, b: int, sched: EpisodeSchedule):
         """Mirror of cluster.reset + first _get_next_job (draw 0 at t=0)."""
@@ -629,6 +634,8 @@ class EngineState:
         self.snapshot[b] = 0
         self.ep_return[b] = 0.0
         self.ep_len[b] = 0
+        self.tp_info[b] = 0.0
+        self.tp_time[b] = 0.0
         self.done[b] = False
         self.status[b] = ST_IDLE
         n = sched.n
@@ -979,6 +986,8 @@ def cpu_step_env(spec: EngineSpec, st: EngineState, b: int,
                      else float(st.t[b]) - t_step_start)
         reward = (tp_acc / step_time
                   if (tp_acc != 0 and step_time != 0) else 0.0)
+        st.tp_info[b] = tp_acc
+        st.tp_time[b] = step_time
     st.reward[b] = reward
     st.ep_return[b] += reward
 
@@ -1195,6 +1204,8 @@ class CpuEngine:
             "obs_mask": torch.from_numpy(st.obs_mask),
             "obs_model": torch.from_numpy(st.obs_model),
             "reward": torch.from_numpy(st.reward),
+            "tp_info": torch.from_numpy(st.tp_info),
+            "tp_time": torch.from_numpy(st.tp_time),
             "done": torch.from_numpy(st.done),
             "status": torch.from_numpy(st.status),
             "log_status": torch.from_numpy(st.log_status),

@@ -44,7 +44,7 @@ enum {
   T_STATIC_OK = 0, T_SHAPE_PTR, T_SHAPES,
   T_MODEL_GF, T_MODEL_SEQ, T_MODEL_A2MD, T_MODEL_SEQ_LEN,
   T_OP_MEM, T_PAR_PTR, T_PAR_IDX,
-  T_MD_SPLITS, T_MD_PJSEQ, T_MD_DEGREE, T_MD_MODEL,
+  T_MD_SPLITS, T_MD_PJSEQ, T_MD_DEGREE, T_MD_MODEL, T_MD_TPQ,
   T_HASH_KEYS, T_HASH_VALS,
   T_SCH_MODEL, T_SCH_FRAC, T_SCH_ACC, T_SCH_NOMINAL, T_SCH_N, T_SCH_PARAMS,
   T_T, T_NEXT_ARRIVE, T_ARR_PTR, T_QUEUED, T_N_RUNNING,
@@ -53,14 +53,14 @@ enum {
   T_LOG_STATUS, T_LOG_MD, T_LOG_T_ARR, T_LOG_T_END, T_LOG_ORDER,
   T_ORDER_COUNTER,
   T_OBS_MODEL, T_OBS_SCHED, T_OBS_GF, T_OBS_MASK,
-  T_REWARD, T_STEP_DONE, T_ACTIONS,
+  T_REWARD, T_STEP_DONE, T_TP_INFO, T_TP_TIME, T_ACTIONS,
   T_COUNT
 };
 
 enum {  // iscal indices
   I_B = 0, I_C, I_R, I_S, I_W, I_WW, I_A, I_K, I_SEQ_CAP, I_PAR_CAP,
   I_SCH, I_NJOBS, I_HS, I_INFINITE, I_R_INVERSE, I_R_LOG, I_R_NORMALISER,
-  I_R_FAIL_IS_SEQ, I_COUNT
+  I_R_FAIL_IS_SEQ, I_R_TP_KIND, I_COUNT
 };
 enum {  // fscal indices
   F_EPS = 0, F_MAX_SIM, F_MEM_CAP, F_R_SIGN, F_R_FAIL_FACTOR, F_R_FAIL_CONST,
@@ -83,6 +83,7 @@ struct EnvPtrs {
   const double* md_pjseq;         // [D]
   const int* md_degree;           // [D]
   const int* md_model;            // [D]
+  const double* md_tpq;           // [D] throughput quantity per running job
   const long* hash_keys;          // [HS]
   const double* hash_vals;        // [HS,4]
   // schedules
@@ -101,12 +102,14 @@ struct EnvPtrs {
   int* log_order; int* order_counter;
   int* obs_model; int* obs_sched; float* obs_gf; float* obs_mask;
   double* reward; uint8_t* step_done;
+  double* tp_info; double* tp_time;  // [B] throughput numerator/denominator
   const int* actions;
 };
 
 struct EnvDims {
   int B, C, R, S, W, WW, A, K, SEQ_CAP, PAR_CAP, SCH, NJOBS, HS;
   int infinite_pool, r_inverse, r_log, r_normaliser, r_fail_is_seq;
+  int r_tp_kind;   // 0 none, 1 compute, 2 cluster, 3 demand_total
   double eps, max_sim, mem_cap, r_sign, r_fail_factor, r_fail_const,
          r_acc_success, r_acc_fail, r_jct_w, r_blk_w;
 };
@@ -244,6 +247,18 @@ __device__ int search_placement(const EnvPtrs& P, const EnvDims& D,
     if ((seen[s >> 6] >> (unsigned)(s & 63)) & 1ull)
       out_union[n_union++] = (short)s;
   return n_union;
+}
+
+// The throughput accrual `acc += q * frac` is two roundings in the mirror
+// (product, then sum).  hipcc's default -ffp-contract=fast would make it one
+// fused multiply-add, which changes reward bits once two jobs run at the same
+// time.  HIP's __dmul_rn() is a plain `x * y` without OCML's rounded
+// operations and contracts just the same, so the product is pinned the way
+// cached_step.hip's f32 mul_rn() pins it.
+__device__ __forceinline__ double mul_rn(double a, double b) {
+  double p = a * b;
+  asm("" : "+v"(p));   // opaque to the optimiser: stays a rounded product
+  return p;
 }
 
 // ---- reward (mirror of _jct_reward) ----
@@ -407,9 +422,12 @@ env_step_kernel(EnvPtrs P, EnvDims D) {
   }
   if (D.r_blk_w != 0.0)
     reward += D.r_blk_w * (placed ? D.r_acc_success : D.r_acc_fail);
-  P.reward[b] = reward;
-  P.ep_return[b] += reward;
   P.ep_len[b] += 1;
+  // throughput family: the reward is the FIRST cluster step's
+  // info_processed / step_time, accrued tick by tick in the loop below
+  double tp_acc = 0.0, tp_time = 0.0;
+  bool tp_closed = false;
+  const double t_start = P.t[b];
 
   // ---- outer event loop (+ idle fast-forward) ----
   bool done = false;
@@ -427,6 +445,15 @@ env_step_kernel(EnvPtrs P, EnvDims D) {
     for (int w = 0; w < D.WW; ++w)
       pc += __popcll(P.occ[(long)b * D.WW + w]);
     P.snapshot[b] = pc;
+    if (D.r_tp_kind != 0 && !tp_closed) {
+      // per running job (slot order): frac = tick/jct, info += q * frac;
+      // product and sum round separately, as in the mirror (see mul_rn)
+      for (int s = 0; s < nr; ++s) {
+        long si = (long)b * D.K + s;
+        double frac = tick / P.slot_jct[si];
+        tp_acc = tp_acc + mul_rn(P.md_tpq[P.slot_md[si]], frac);
+      }
+    }
     P.t[b] = P.t[b] + tick;
     // completions (order-preserving compaction)
     int keep = 0;
@@ -471,8 +498,24 @@ env_step_kernel(EnvPtrs P, EnvDims D) {
     pool_empty = (!D.infinite_pool) && isinf(P.next_arrive[b]);
     done = (P.t[b] >= D.max_sim) ||
            (pool_empty && P.n_running[b] == 0 && P.queued[b] < 0);
+    // a cluster step ends at the first completion or arrival (or done);
+    // later iterations are idle fast-forward and accrue nothing
+    if (D.r_tp_kind != 0 && !tp_closed &&
+        (keep != nr || P.queued[b] >= 0 || done)) {
+      tp_time = P.t[b] - t_start;
+      tp_closed = true;
+    }
     if (P.queued[b] >= 0 || done) break;
   }
+
+  if (D.r_tp_kind != 0) {
+    double step_time = tp_closed ? tp_time : P.t[b] - t_start;
+    reward = (tp_acc != 0.0 && step_time != 0.0) ? tp_acc / step_time : 0.0;
+    P.tp_info[b] = tp_acc;
+    P.tp_time[b] = step_time;
+  }
+  P.reward[b] = reward;
+  P.ep_return[b] += reward;
 
   if (done) {
     // finalise: still-running jobs become blocked (reference :1111-1121)
@@ -513,6 +556,7 @@ void env_step_batch(std::vector<torch::Tensor> T,
   D.r_inverse = (int)iscal[I_R_INVERSE]; D.r_log = (int)iscal[I_R_LOG];
   D.r_normaliser = (int)iscal[I_R_NORMALISER];
   D.r_fail_is_seq = (int)iscal[I_R_FAIL_IS_SEQ];
+  D.r_tp_kind = (int)iscal[I_R_TP_KIND];
   D.eps = fscal[F_EPS]; D.max_sim = fscal[F_MAX_SIM];
   D.mem_cap = fscal[F_MEM_CAP]; D.r_sign = fscal[F_R_SIGN];
   D.r_fail_factor = fscal[F_R_FAIL_FACTOR];
@@ -537,6 +581,7 @@ void env_step_batch(std::vector<torch::Tensor> T,
   P.md_pjseq = T[T_MD_PJSEQ].data_ptr<double>();
   P.md_degree = T[T_MD_DEGREE].data_ptr<int>();
   P.md_model = T[T_MD_MODEL].data_ptr<int>();
+  P.md_tpq = T[T_MD_TPQ].data_ptr<double>();
   P.hash_keys = T[T_HASH_KEYS].data_ptr<long>();
   P.hash_vals = T[T_HASH_VALS].data_ptr<double>();
   P.sch_model = T[T_SCH_MODEL].data_ptr<int>();
@@ -573,7 +618,13 @@ void env_step_batch(std::vector<torch::Tensor> T,
   P.obs_mask = T[T_OBS_MASK].data_ptr<float>();
   P.reward = T[T_REWARD].data_ptr<double>();
   P.step_done = T[T_STEP_DONE].data_ptr<uint8_t>();
+  P.tp_info = T[T_TP_INFO].data_ptr<double>();
+  P.tp_time = T[T_TP_TIME].data_ptr<double>();
   P.actions = T[T_ACTIONS].data_ptr<int>();
+  TORCH_CHECK(T[T_MD_TPQ].numel() == T[T_MD_MODEL].numel(),
+              "env_step: md_tpq must have one entry per (model, degree)");
+  TORCH_CHECK(T[T_TP_INFO].numel() == D.B && T[T_TP_TIME].numel() == D.B,
+              "env_step: tp_info / tp_time must be [B]");
 
   const int MAXS = D.A - 1;
   size_t shmem = (size_t)D.W * sizeof(double)

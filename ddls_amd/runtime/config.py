@@ -147,8 +147,9 @@ def build_trainer_from_config(cfg: dict, device=None):
     # env backend: "engine" = vectorised engine (GPU kernel on cuda,
     # CpuEngine mirror on cpu), "subproc" = fork-based env workers,
     # "auto" (default) = engine on cuda, subprocess on cpu (historical
-    # default; the engine supports 1-channel RAMP + the non-throughput
-    # rewards — unsupported configs raise with a clear message)
+    # default; the engine supports 1-channel RAMP with every reward
+    # function, the throughput family included — unsupported configs
+    # raise with a clear message)
     backend = loop_cfg.get("env_backend", "auto")
     use_cuda = (device is not None and str(device) != "cpu"
                 and torch.cuda.is_available())
@@ -162,9 +163,9 @@ def build_trainer_from_config(cfg: dict, device=None):
                                    else torch.device("cpu"),
                                    base_seed=seed)
         except ValueError:
-            # engine-unsupported config (throughput reward, multi-channel,
-            # non-RAMP): explicit request surfaces the error, auto falls
-            # back to the subprocess path
+            # engine-unsupported config (multi-channel, non-RAMP): explicit
+            # request surfaces the error, auto falls back to the subprocess
+            # path
             if backend == "engine":
                 raise
             use_engine = False
