@@ -65,6 +65,10 @@ void env_step_batch(std::vector<torch::Tensor> T, std::vector<double> fscal,
                     std::vector<int64_t> iscal);
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs);
 void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs);
+void cached_stage(std::vector<torch::Tensor> store,
+                  std::vector<torch::Tensor> dst, torch::Tensor perm,
+                  torch::Tensor cursor, torch::Tensor err,
+                  std::vector<torch::Tensor> dims);
 std::vector<torch::Tensor> lookahead_batch(
     torch::Tensor descs, torch::Tensor op_remaining, torch::Tensor op_worker,
     torch::Tensor op_priority, torch::Tensor out_indptr, torch::Tensor out_edges,
@@ -109,6 +113,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fully-fused cached-models PPO minibatch forward (GNN+head+loss)");
     m.def("cached_step_bwd", &cached_step_bwd,
           "analytic whole-net backward into the flat grad buffer");
+    m.def("cached_stage", &cached_stage,
+          "gather one minibatch from the device batch store into the "
+          "cached step's staged inputs; advances the device cursor");
     m.def("env_step_batch", &env_step_batch,
           "batched RAMP env step over vectorised envs (placement search + "
           "memo hash probe + event loop + obs encode)");

@@ -27,8 +27,43 @@ from ..models.gnn import GraphBatch, graph_mean
 from .rollout import CompactObs
 
 
+class LazyObsSeq:
+    """``data["obs"]`` of a device-resident rollout: a read-only sequence of
+    CompactObs that is only materialised (ONE D2H copy of the flat gfull and
+    model-id tensors) the first time something indexes it.  The device PPO
+    update never does; the eager loop, partial minibatches and host-staged
+    test helpers index it exactly like the host list."""
+
+    def __init__(self, env, gfull: torch.Tensor, model_ids: torch.Tensor):
+        self._env = env
+        self._gfull = gfull
+        self._model_ids = model_ids
+        self._items = None
+
+    def __len__(self):
+        return int(self._gfull.shape[0])
+
+    def _materialise(self):
+        if self._items is None:
+            gfull = self._gfull.cpu().numpy()
+            mids = self._model_ids.cpu().numpy()
+            self._items = [self._env._compact(int(mids[i]), gfull[i],
+                                              gfull[i, 17:])
+                           for i in range(len(mids))]
+        return self._items
+
+    def __getitem__(self, i):
+        return self._materialise()[i]
+
+    def __iter__(self):
+        return iter(self._materialise())
+
+
 class EngineVectorEnv:
     """Same trainer-facing API as SubprocVectorEnv, GPU-resident."""
+
+    # rollout() takes device_resident=True (PPOTrainer's device-batch path)
+    supports_device_resident = True
 
     def __init__(self, env_fn, num_envs: int, device, base_seed: int = 0,
                  spec=None, proto_env=None, verbose: bool = False):
@@ -135,7 +170,12 @@ class EngineVectorEnv:
         return logits, value
 
     @torch.no_grad()
-    def rollout(self, policy, steps: int) -> Dict[str, np.ndarray]:
+    def rollout(self, policy, steps: int,
+                device_resident: bool = False) -> Dict[str, np.ndarray]:
+        """``device_resident=True`` keeps the per-sample training inputs as
+        flat ``[T*B, ...]`` tensors on the engine's device (keys ``*_dev``)
+        and returns ``obs`` as a LazyObsSeq instead of building T*B
+        CompactObs; sampling and everything GAE needs are unchanged."""
         dev = self.device
         B = self.num_envs
         A = self.spec.A
@@ -191,6 +231,26 @@ class EngineVectorEnv:
         _, bootstrap = self._head_forward(policy, model_emb,
                                           eng.T["obs_model"].long(), gfull,
                                           mask)
+
+        if device_resident:
+            n = T * B
+            gfull_dev = buf_gfull.reshape(n, 17 + A)
+            model_dev = buf_model.reshape(n)
+            return {
+                "obs": LazyObsSeq(self, gfull_dev, model_dev),
+                "gfull_dev": gfull_dev,
+                "model_ids_dev": model_dev,
+                "actions_dev": buf_actions.reshape(n),
+                "logp_dev": buf_logp.reshape(n),
+                "lp_all_dev": buf_lp_all.reshape(n, A),
+                "actions": buf_actions.cpu().numpy(),
+                "lp_all": buf_lp_all.cpu().numpy(),
+                "logp": buf_logp.cpu().numpy(),
+                "values": buf_values.cpu().numpy(),
+                "rewards": buf_rewards.cpu().numpy(),
+                "dones": buf_dones.cpu().numpy(),
+                "bootstrap_values": bootstrap.cpu().numpy(),
+            }
 
         # D2H once; build CompactObs over shared per-model arrays
         gfull_np = buf_gfull.cpu().numpy()

@@ -204,11 +204,152 @@ class _FusedCachedEngine:
         self.ext.cached_step_bwd(self.scratch, self.fscal)
 
 
+class DeviceBatchStore:
+    """Fixed-capacity, fixed-address train batch for the captured PPO step.
+
+    The rollout's per-sample inputs stay on the device; ``bind()`` refills
+    the store once per update (D2D for what the rollout left there, one H2D
+    copy each for the standardised advantages, the value targets and the
+    permutation table) and ops/hip/batch_stage.hip gathers one minibatch per
+    graph replay: row i of minibatch k is store row ``perm[k, i]``, k being
+    the device-side ``cursor`` the kernel advances itself.
+
+    ``n_rows`` / ``n_mb`` are device scalars, so a captured graph survives a
+    change of batch size within capacity.  ``perm`` holds ``cap_mb`` rows:
+    the minibatches of one update plus one spare row, so the position one
+    past a full table still lies inside the allocation.
+
+    ``cursor == BYPASS`` turns the stage kernel into a no-op: that is how the
+    host-staged API (``step``/``prepare``/``commit``) keeps working on a
+    stepper whose captured graph starts with the stage node.
+    """
+
+    BYPASS = -1          # CS_STAGE_BYPASS in ops/hip/batch_stage.hip
+    ERR_NAMES = {1: "cursor outside the permutation table",
+                 2: "row index outside the bound batch"}
+
+    def __init__(self, cap_n: int, cap_mb: int, B: int, Fg: int, A: int,
+                 device):
+        self.cap_n, self.cap_mb = int(cap_n), int(cap_mb)
+        self.B, self.Fg, self.A = int(B), int(Fg), int(A)
+        self.device = torch.device(device)
+        dev = self.device
+
+        def z(shape, dtype):
+            return torch.zeros(shape, dtype=dtype, device=dev)
+
+        self.gfull = z((self.cap_n, self.Fg), torch.float32)
+        self.model_ids = z(self.cap_n, torch.int64)
+        self.actions = z(self.cap_n, torch.int64)
+        self.old_logp = z(self.cap_n, torch.float32)
+        self.adv = z(self.cap_n, torch.float32)
+        self.vtarg = z(self.cap_n, torch.float32)
+        self.perm = z((self.cap_mb, self.B), torch.int32)
+        # one allocation for the four control words
+        self._ctl = z(4, torch.int32)
+        self.cursor, self.err = self._ctl[0:1], self._ctl[1:2]
+        self.n_rows, self.n_mb = self._ctl[2:3], self._ctl[3:4]
+        self.n = 0               # host mirrors of n_rows / n_mb
+        self.num_mb = 0
+        self.bypass = False      # host mirror of cursor == BYPASS
+        self.h2d_copies = 0      # host->device copies issued by bind()
+
+    @property
+    def bound(self) -> bool:
+        return self.num_mb > 0
+
+    def tensors(self):
+        """The store fields in the order ``cached_stage`` takes them."""
+        return [self.gfull, self.model_ids, self.actions, self.old_logp,
+                self.adv, self.vtarg]
+
+    def _put(self, dst: torch.Tensor, src):
+        if not torch.is_tensor(src):
+            src = torch.from_numpy(np.ascontiguousarray(src))
+        if dst.is_cuda and not src.is_cuda:
+            self.h2d_copies += 1
+        dst.copy_(src)
+
+    def bind(self, gfull, model_ids, actions, old_logp, adv, vtarg, perm):
+        """Refill the store with an ``n``-row batch and its ``[n_mb, B]``
+        permutation table, and rewind the cursor.  Device tensors are copied
+        D2D; numpy / CPU inputs cost one H2D copy each."""
+        n = int(gfull.shape[0])
+        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, self.B)
+        n_mb = int(perm.shape[0])
+        if not 0 < n <= self.cap_n:
+            raise ValueError(f"batch of {n} rows does not fit the store "
+                             f"(capacity {self.cap_n})")
+        if not 0 < n_mb <= self.cap_mb - 1:
+            raise ValueError(f"{n_mb} minibatches do not fit the store "
+                             f"(capacity {self.cap_mb - 1} + 1 spare)")
+        if perm.min() < 0 or perm.max() >= n:
+            raise ValueError("permutation table indexes outside the batch")
+        self._put(self.gfull[:n], gfull)
+        self._put(self.model_ids[:n], model_ids)
+        self._put(self.actions[:n], actions)
+        self._put(self.old_logp[:n], old_logp)
+        self._put(self.adv[:n], adv)
+        self._put(self.vtarg[:n], vtarg)
+        self._put(self.perm[:n_mb], perm)
+        self.n, self.num_mb = n, n_mb
+        self.n_rows.fill_(n)
+        self.n_mb.fill_(n_mb)
+        self.reset()
+
+    def reset(self):
+        """Rewind the cursor to the first minibatch and clear ``err``."""
+        self.cursor.zero_()
+        self.err.zero_()
+        self.bypass = False
+
+    def set_bypass(self):
+        if not self.bypass:
+            self.cursor.fill_(self.BYPASS)
+            self.bypass = True
+
+    def stage_into(self, ext, d):
+        """Launch the stage kernel: gather minibatch ``cursor`` into the
+        staged-input buffers ``d`` and advance the cursor."""
+        ext.cached_stage(self.tensors(),
+                         [d["gf"], d["mask"], d["model_ids"], d["actions"],
+                          d["old_logp"], d["adv"], d["vtarg"]],
+                         self.perm, self.cursor, self.err,
+                         [self.n_rows, self.n_mb])
+
+    def check_err(self):
+        code = int(self.err.item())
+        if code != 0:
+            raise RuntimeError(
+                f"device batch stage kernel reported error code {code} "
+                f"({self.ERR_NAMES.get(code, 'unknown')})")
+
+
+def stage_reference(store: DeviceBatchStore, perm: torch.Tensor,
+                    cursor: int) -> dict:
+    """What the stage kernel must write for minibatch ``cursor`` of the
+    table ``perm``: index_select per field plus the mask slice (pure torch,
+    any device)."""
+    idx = perm[cursor].to(device=store.gfull.device, dtype=torch.int64)
+    gf = store.gfull.index_select(0, idx)
+    return {"gf": gf,
+            "mask": gf[:, store.Fg - store.A:].contiguous(),
+            "model_ids": store.model_ids.index_select(0, idx),
+            "actions": store.actions.index_select(0, idx),
+            "old_logp": store.old_logp.index_select(0, idx),
+            "adv": store.adv.index_select(0, idx),
+            "vtarg": store.vtarg.index_select(0, idx)}
+
+
 class CapturedSGDStep:
     """Replayable hipGraph of one PPO SGD minibatch step.
 
     ``step()`` returns False (caller runs the eager path) when the minibatch
     is partial, capture is unsupported, or a capture attempt failed.
+
+    With a ``device_store`` (cached-models mode only) the captured body
+    starts with the minibatch stage kernel and ``replay_next()`` trains on
+    the store's next minibatch with nothing but the graph replay.
     """
 
     GROWTH = 1.3
@@ -218,7 +359,18 @@ class CapturedSGDStep:
     # ghn atomics
     RESERVE = 256
 
-    def __init__(self, policy, optimizer, config, device, models_batch=None):
+    def __init__(self, policy, optimizer, config, device, models_batch=None,
+                 device_store: Optional[DeviceBatchStore] = None):
+        if device_store is not None:
+            if models_batch is None:
+                raise ValueError("device_store needs cached-models mode "
+                                 "(models_batch)")
+            if device_store.B != config.sgd_minibatch_size:
+                raise ValueError("device_store minibatch size differs from "
+                                 "config.sgd_minibatch_size")
+        self.store = device_store
+        # host->device copies issued by commit() (the store counts its own)
+        self._commit_h2d = 0
         self.policy = policy
         self.optimizer = optimizer
         self.cfg = config
@@ -336,13 +488,49 @@ class CapturedSGDStep:
 
     def commit(self, j: int):
         """Enqueue H2D copies from pinned set j + replay the graph."""
+        if self.store is not None:
+            # the graph starts with the stage node: make it a no-op so the
+            # rows uploaded below are what the step reads
+            self.store.set_bypass()
         if self.models_batch is not None:
             self._flat_f32.copy_(self.pin[j]["_flat_f32"], non_blocking=True)
             self._flat_i64.copy_(self.pin[j]["_flat_i64"], non_blocking=True)
+            self._commit_h2d += 2
         else:
             for k, dst_t in self.d.items():
                 dst_t.copy_(self.pin[j][k], non_blocking=True)
+            self._commit_h2d += len(self.d)
         self.copy_events[j].record()
+        self._replay()
+
+    def replay_next(self):
+        """Train on the store's next minibatch: the graph replay gathers it
+        (stage kernel) and advances the cursor.  No host staging, no
+        copies."""
+        if self.store is None or self.graph is None:
+            raise RuntimeError("replay_next() needs a device store and a "
+                               "captured graph")
+        if self.store.bypass:
+            raise RuntimeError("replay_next() after a host-staged commit(): "
+                               "bind() or reset() the store first")
+        self._replay()
+
+    @property
+    def h2d_copies(self) -> int:
+        """Host->device copies issued so far by commit() and by the
+        store's bind()."""
+        return self._commit_h2d + (self.store.h2d_copies
+                                   if self.store is not None else 0)
+
+    def read_stats(self) -> np.ndarray:
+        """The per-update host sync: the summed loss statistics, and with a
+        device store the stage kernel's error word."""
+        acc = self.stats_acc.cpu().numpy()
+        if self.store is not None:
+            self.store.check_err()
+        return acc
+
+    def _replay(self):
         self.graph.replay()
         if self.graph_opt is not None:
             if self.flat_p is not None:
@@ -532,6 +720,12 @@ class CapturedSGDStep:
 
     def _body_fwd_bwd(self):
         cfg, B = self.cfg, self.B
+        if self.store is not None:
+            # first node of the chain: gather this minibatch's rows from the
+            # device batch store into the d-buffers everything below reads
+            from .. import ops as hip_ops
+            self.store.stage_into(hip_ops.get_extension(required=True),
+                                  self.d)
         if self._fused_cached is not None:
             # fully-fused path: two kernels, grads straight into flat_g
             self._fused_cached.run()
@@ -711,6 +905,16 @@ class CapturedSGDStep:
             if not split:
                 self._body_opt()
 
+        def rewind():
+            # warmup and capture runs gather REAL rows (minibatch 0 of the
+            # bound table); an unbound store is bypassed instead
+            if self.store is None:
+                return
+            if self.store.bound:
+                self.store.reset()
+            else:
+                self.store.set_bypass()
+
         saved_stats = self.stats_acc.clone()
         if self._flat_engine:
             self._flatten_params()
@@ -729,6 +933,7 @@ class CapturedSGDStep:
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 for _ in range(3):
+                    rewind()
                     whole()
                     if split:
                         self._body_opt()
@@ -758,6 +963,7 @@ class CapturedSGDStep:
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
                     for _ in range(3):
+                        rewind()
                         whole()
                         if split:
                             self._body_opt()
@@ -780,6 +986,7 @@ class CapturedSGDStep:
                         v.zero_()
         self.stats_acc.copy_(saved_stats)
 
+        rewind()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             whole()
@@ -789,5 +996,6 @@ class CapturedSGDStep:
                 self._body_opt()
         # discard warmup/capture side effects on the accumulator
         self.stats_acc.copy_(saved_stats)
+        rewind()   # cursor back to minibatch 0, err cleared
         self.capture_count += 1
         torch.cuda.synchronize()

@@ -42,6 +42,12 @@ class PPOConfig:
     # capture the SGD minibatch step in a hipGraph on GPU (graph_step.py);
     # eager fallback on CPU / partial minibatches / capture failure
     use_hip_graphs: bool = True
+    # train from a device-resident rollout batch (graph_step.DeviceBatchStore
+    # + ops/hip/batch_stage.hip): "auto" takes the device path whenever it is
+    # eligible and today's host-staged path otherwise, "on" does the same but
+    # says so on stderr when it has to fall back, "off" is the host-staged
+    # path exactly.  DDLS_AMD_DISABLE_DEVICE_BATCH=1 forces "off".
+    device_batch: str = "auto"
 
 
 class PPOTrainer:
@@ -65,6 +71,10 @@ class PPOTrainer:
         self.iteration = 0
         self._stepper = None  # lazy CapturedSGDStep (GPU only)
         self._mb_executor = None  # prefetch thread for captured minibatches
+        if self.config.device_batch not in ("auto", "on", "off"):
+            raise ValueError("PPOConfig.device_batch must be 'auto', 'on' "
+                             f"or 'off', not {self.config.device_batch!r}")
+        self._device_batch_warned = False
 
     # ------------------------------------------------------------------
     @torch.no_grad()
@@ -84,6 +94,23 @@ class PPOTrainer:
                                         inputs["action_mask"])
 
     # ------------------------------------------------------------------
+    def _device_batch_wanted(self) -> bool:
+        """Whether to ask the env for a device-resident rollout: the part of
+        the device-batch gate that is known before the batch exists."""
+        cfg = self.config
+        return (cfg.device_batch != "off"
+                and os.environ.get("DDLS_AMD_DISABLE_DEVICE_BATCH", "0") != "1"
+                and cfg.use_hip_graphs
+                and self.device.type == "cuda" and torch.cuda.is_available()
+                and getattr(self.env, "supports_device_resident", False))
+
+    def _device_batch_fallback(self, why: str):
+        if self.config.device_batch == "on" and not self._device_batch_warned:
+            import sys
+            print(f"[ppo] device_batch='on' but taking the host-staged path: "
+                  f"{why}", file=sys.stderr)
+            self._device_batch_warned = True
+
     def collect_rollout(self, num_steps: Optional[int] = None) -> Dict[str, np.ndarray]:
         """Collect num_steps per-rank env steps across the vectorised envs."""
         cfg = self.config
@@ -94,7 +121,11 @@ class PPOTrainer:
         if hasattr(self.env, "rollout"):
             # RLlib-style worker-side rollouts: policy copies live in the env
             # workers; one IPC round trip per iteration
-            data = self.env.rollout(self.policy, steps)
+            if self._device_batch_wanted():
+                data = self.env.rollout(self.policy, steps,
+                                        device_resident=True)
+            else:
+                data = self.env.rollout(self.policy, steps)
             self.total_env_steps += steps * n_envs
             rewards, dones = data["rewards"], data["dones"]
             values, logps, actions = data["values"], data["logp"], data["actions"]
@@ -122,6 +153,11 @@ class PPOTrainer:
             if "lp_all" in data:
                 lp = np.asarray(data["lp_all"])
                 out["lp_all"] = lp.reshape(-1, lp.shape[-1])
+            # device-resident rollout: flat [T*B, ...] device tensors
+            for k in ("gfull_dev", "model_ids_dev", "actions_dev",
+                      "logp_dev", "lp_all_dev"):
+                if k in data:
+                    out[k] = data[k]
             return out
 
         obs_buf: List[CompactObs] = []
@@ -201,6 +237,10 @@ class PPOTrainer:
         # hipGraph-captured minibatch step (GPU): one replay per minibatch
         # instead of ~120 host-dispatched kernel launches
         stepper = None
+        B = cfg.sgd_minibatch_size
+        # device-batch path: the rollout's tensors never left the device
+        dev_batch = ("gfull_dev" in batch and self._device_batch_wanted()
+                     and n >= B and n % B == 0)
         if (cfg.use_hip_graphs and self.device.type == "cuda"
                 and torch.cuda.is_available()):
             if self._stepper is None:
@@ -208,31 +248,55 @@ class PPOTrainer:
                 # cached-models mode when the env serves per-model static
                 # obs (vectorised engine): GNN once per model per minibatch
                 mb_static = getattr(self.env, "_models_batch", None)
-                if mb_static is not None and batch["obs"] \
+                if mb_static is not None and "gfull_dev" not in batch \
+                        and batch["obs"] \
                         and getattr(batch["obs"][0], "model_id", -1) < 0:
                     mb_static = None
+                store = None
+                if dev_batch and mb_static is not None:
+                    store = self._make_device_store(n)
                 self._stepper = CapturedSGDStep(self.policy, self.optimizer,
                                                 cfg, self.device,
-                                                models_batch=mb_static)
+                                                models_batch=mb_static,
+                                                device_store=store)
             stepper = self._stepper
             stepper.reset_stats()
             stepper.set_kl_coeff(self.kl_coeff)
+        n_mb = cfg.num_sgd_iter * (n // B) if B > 0 else 0
+        dev_batch = (dev_batch and stepper is not None
+                     and stepper.store is not None and not stepper.broken
+                     and n <= stepper.store.cap_n
+                     and n_mb <= stepper.store.cap_mb - 1)
+        if not dev_batch and cfg.device_batch == "on":
+            self._device_batch_fallback(
+                "needs the engine env on a GPU, the fused cached step, a "
+                "batch that is a multiple of the minibatch size and fits "
+                "the store sized at the first update")
+        h2d_before = stepper.h2d_copies if stepper is not None else 0
         actions_np = np.asarray(batch["actions"], dtype=np.int64)
         logp_np = np.asarray(batch["logp"], dtype=np.float32)
         adv_np = np.asarray(adv, dtype=np.float32)
         vtarg_np = np.asarray(batch["value_targets"], dtype=np.float32)
 
         rng = np.random.RandomState(self.iteration + 1234 * get_rank())
-        B = cfg.sgd_minibatch_size
 
         captured = False
+        on_device = False
         if stepper is not None and not stepper.broken and n >= B and n % B == 0:
             idx_lists = []
             for _ in range(cfg.num_sgd_iter):
                 perm = rng.permutation(n)
                 for start in range(0, n, B):
                     idx_lists.append(perm[start:start + B])
-            if stepper.models_batch is not None:
+            if dev_batch:
+                # refill the store BEFORE the (first-update) capture: its
+                # warmup runs gather real rows through the stage kernel.
+                # Same permutation stream as the host path, uploaded once.
+                stepper.store.bind(batch["gfull_dev"], batch["model_ids_dev"],
+                                   batch["actions_dev"], batch["logp_dev"],
+                                   adv_np, vtarg_np, np.stack(idx_lists))
+                captured = on_device = stepper.ensure_capacity(0, 0)
+            elif stepper.models_batch is not None:
                 # cached-models mode: fixed shapes, single capture
                 captured = stepper.ensure_capacity(0, 0)
             else:
@@ -250,6 +314,16 @@ class PPOTrainer:
                                                    int(need_e * 1.05) + 8)
             if not captured:  # replay the same permutation stream eagerly
                 rng = np.random.RandomState(self.iteration + 1234 * get_rank())
+
+        if on_device:
+            # device-batch loop: every replay gathers its own minibatch from
+            # the store — no host staging, no copies, no prefetch thread
+            for _ in range(len(idx_lists)):
+                stepper.replay_next()
+            num_updates += len(idx_lists)
+            num_captured += len(idx_lists)
+            rng = None
+            captured = False
 
         if captured and os.environ.get("DDLS_AMD_DISABLE_PREFETCH", "0") == "1":
             for idx in idx_lists:
@@ -339,7 +413,8 @@ class PPOTrainer:
                     num_updates += 1
 
         if num_captured:
-            acc = self._stepper.stats_acc.cpu().numpy()  # one sync per update
+            # one sync per update; also raises on a stage-kernel error
+            acc = self._stepper.read_stats()
             for k, v in zip(("policy_loss", "vf_loss", "kl", "entropy",
                              "total_loss"), acc):
                 stats[k] += float(v)
@@ -352,7 +427,8 @@ class PPOTrainer:
         kl_for_adapt = stats["kl"]
         if batch.get("lp_all") is not None:
             try:
-                kl_an = self._analytic_kl(batch)
+                kl_an = self._analytic_kl(
+                    batch, store=stepper.store if on_device else None)
                 stats["kl_analytic"] = kl_an
                 kl_for_adapt = kl_an
             except Exception:
@@ -365,16 +441,66 @@ class PPOTrainer:
         if stepper is not None:
             stats["hipgraph_minibatches"] = num_captured
             stats["hipgraph_captures"] = stepper.capture_count
+            # H2D copies the stepper issued for this update: 2 per minibatch
+            # host-staged, a small constant on the device-batch path
+            stats["staged_h2d_copies"] = stepper.h2d_copies - h2d_before
+        stats["device_batch"] = int(on_device)
         return stats
+
+    def _make_device_store(self, n: int):
+        """A DeviceBatchStore sized for the train batch, or None when the
+        stepper would not run the fused cached step (the device-batch path
+        is only offered on top of it)."""
+        from .. import ops as hip_ops
+        from .graph_step import DeviceBatchStore, _FusedCachedEngine
+        cfg = self.config
+        try:
+            ext = hip_ops.get_extension()
+        except Exception:
+            ext = None
+        if (ext is None or not hasattr(ext, "cached_stage")
+                or not hasattr(ext, "flat_adam")
+                or os.environ.get("DDLS_AMD_DISABLE_FLAT_ADAM", "0") == "1"
+                or not _FusedCachedEngine.eligible(self.policy, ext)):
+            return None
+        B = cfg.sgd_minibatch_size
+        cap_n = max(n, (cfg.train_batch_size // B) * B)
+        # every minibatch of one update, plus one spare row
+        cap_mb = cfg.num_sgd_iter * (cap_n // B) + 1
+        A = self.policy.num_actions
+        return DeviceBatchStore(
+            cap_n, cap_mb, B, self.policy.config["in_features_graph"] + A, A,
+            self.device)
 
     # ------------------------------------------------------------------
     @torch.no_grad()
-    def _analytic_kl(self, batch: Dict) -> float:
+    def _analytic_kl(self, batch: Dict, store=None) -> float:
         """KL(old || new) = E_old[sum_a p_old (lp_old - lp_new)] over the
-        train batch, with the post-update policy."""
+        train batch, with the post-update policy.  With ``store`` (the
+        device-batch path) the inputs are read from the bound
+        DeviceBatchStore instead of being re-stacked and uploaded."""
+        mb_static = getattr(self.env, "_models_batch", None)
+        if store is not None:
+            from ..models.gnn import graph_mean
+            n = store.n
+            old_lp = batch["lp_all_dev"]
+            node_emb = self.policy.gnn(mb_static)
+            model_emb = graph_mean(node_emb, mb_static)
+            gfull = store.gfull[:n]
+            mask = gfull[:, store.Fg - store.A:]
+            graph_emb = self.policy.graph_module(gfull)
+            final = torch.cat([model_emb[store.model_ids[:n]], graph_emb],
+                              dim=-1)
+            logits = self.policy.policy_branch(final)
+            if self.policy.config["apply_action_mask"]:
+                logits = logits + torch.clamp(
+                    torch.log(mask), min=torch.finfo(torch.float32).min)
+            new_lp = F.log_softmax(logits, dim=-1)
+            p_old = torch.exp(old_lp)
+            kl = (p_old * (old_lp - new_lp)).sum(-1).mean()
+            return float(kl.item())
         obs = batch["obs"]
         old_lp = torch.as_tensor(batch["lp_all"], device=self.device)
-        mb_static = getattr(self.env, "_models_batch", None)
         if mb_static is not None and getattr(obs[0], "model_id", -1) >= 0:
             # cached-models forward: GNN once over the model graphs
             from ..models.gnn import graph_mean

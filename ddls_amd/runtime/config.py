@@ -242,5 +242,9 @@ def build_trainer_from_config(cfg: dict, device=None):
         grad_clip=algo.get("grad_clip", 1.5),
         sgd_minibatch_size=algo.get("sgd_minibatch_size", 128),
         train_batch_size=algo.get("train_batch_size", 4000),
-        num_sgd_iter=algo.get("num_sgd_iter", 50))
+        num_sgd_iter=algo.get("num_sgd_iter", 50),
+        # YAML reads a bare on/off as a boolean
+        device_batch={True: "on", False: "off"}.get(
+            algo.get("device_batch", "auto"),
+            str(algo.get("device_batch", "auto"))))
     return PPOTrainer(venv, policy, ppo_cfg, device=device)
