@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #define LN_EPS 1e-5f
@@ -1404,10 +1406,406 @@ cs_bwd_w_reduce_kernel(CachedPtrs P, CachedDims D) {
 }
 
 // ===========================================================================
+// lane-parallel row kernels
+// ===========================================================================
+//
+// The thread-per-row kernels above (cs_fwd_mlp, cs_fwd_reduce, cs_bwd_reduce,
+// cs_bwd_mlp2, cs_bwd_gu1) put the N+E graph rows on two workgroups and run
+// each row's LayerNorm and Din x Dout GEMV as one thread's serial chain.  The
+// kernels below give each row a group of L lanes and a block 256/L rows, so
+// the same work spreads over (N+E)*L/256 workgroups.  They are the default;
+// DDLS_AMD_ROW_KERNELS=thread launches the thread-per-row kernels instead,
+// which stay in the file unchanged as the oracle for bitwise comparison.
+//
+// No sum is re-associated: every output element is still accumulated by one
+// lane in the order the thread-per-row code uses (i ascending for a forward
+// output and the LN sums, o ascending for a gu element); lanes only divide
+// the OUTPUTS among themselves.  The rows of a block are staged in LDS once
+// (row stride +1 so the groups of a wave sit on different banks; the forward
+// weights too, because the lanes of a group read different W rows at one i).
+//
+// Contraction is switched off from here to the end of the file and every
+// rounding is written out, FMA() = one rounding, a + b * c = two.  The
+// pattern per instantiation is the one the thread-per-row build has (read
+// off its gfx950 ISA; docs/KERNELS.md "Round 5" lists it):
+//   LN variance    d0*d0 rounded, then d_i*d_i added as rounded products,
+//                  except the LAST term of a 5-wide row and the 16 zero-half
+//                  terms of a self row, which are fused
+//   var/Din + eps  one FMA when Din is a power of two, divide-then-add for 5
+//   u = xh*gam+bet one FMA; every forward GEMV term fused
+//   gu = W^T gpre  all 16 terms fused (Dout 16, node/edge modules), the first
+//                  4 of 16 (reduce module 2) or the first 52 of 64 (reduce
+//                  module 1) fused and the last 12 rounded products
+//   LN backward    gh = gu*gam rounded inside m1 and m2, gh*xh rounded;
+//                  gin = rstd * FMA(-xh, m2, FMA(gu, gam, -m1)), except the
+//                  last two elements of a 32-wide row, which take the rounded
+//                  gh: FMA(m1sum, -1/32, gh)
+#pragma clang fp contract(off)
+
+#define ROW_NT 256   // block size of every lane-parallel row kernel
+
+// forward of the block's rows [r0, r0 + 256/L) of one row class.  NF = the
+// number of trailing variance terms that are fused.  Called by all threads
+// of the block (barriers inside).
+template <int Din, int Dout, int NF, int L, typename LoadX>
+__device__ __forceinline__ void rows_fwd_lanes(
+    const CachedPtrs& P, int w_slot, long r0, long nrows, LoadX loadx,
+    float* __restrict__ xhat_out, float* __restrict__ rstd_out,
+    float* __restrict__ out) {
+  constexpr int RPB = ROW_NT / L;
+  constexpr int XS = Din + 1;
+  __shared__ float sGam[Din], sBet[Din], sW[Dout * XS], sB[Dout];
+  __shared__ float sX[RPB * XS], sU[RPB * XS];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Din; i += ROW_NT) {
+    sGam[i] = WP(w_slot)[i];
+    sBet[i] = WP(w_slot + 1)[i];
+  }
+  for (int x = tid; x < Din * Dout; x += ROW_NT)
+    sW[(x / Din) * XS + x % Din] = WP(w_slot + 2)[x];
+  for (int o = tid; o < Dout; o += ROW_NT) sB[o] = WP(w_slot + 3)[o];
+  for (int x = tid; x < RPB * Din; x += ROW_NT) {
+    const int r = x / Din, i = x % Din;
+    sX[r * XS + i] = (r0 + r < nrows) ? loadx(r0 + r, i) : 0.f;
+  }
+  __syncthreads();
+  const int g = tid / L, l = tid % L;
+  const long row = r0 + g;
+  const bool live = row < nrows;
+  // LN statistics: every lane of the group walks the whole row in order
+  const float* __restrict__ x = sX + g * XS;
+  float s = 0.f;
+#pragma unroll 8
+  for (int i = 0; i < Din; ++i) s = s + x[i];
+  const float mu = s / Din;
+  float var;
+  {
+    const float d0 = x[0] - mu;
+    var = d0 * d0;
+  }
+#pragma unroll 8
+  for (int i = 1; i < Din; ++i) {
+    const float d = x[i] - mu;
+    if (i >= Din - NF) var = FMA(d, d, var);
+    else var = var + d * d;
+  }
+  float rstd;
+  if ((Din & (Din - 1)) == 0) rstd = rsqrtf(FMA(var, 1.f / Din, LN_EPS));
+  else rstd = rsqrtf(var / Din + LN_EPS);
+  for (int i = l; i < Din; i += L) {
+    const float xh = (x[i] - mu) * rstd;
+    if (live) xhat_out[row * Din + i] = xh;
+    sU[g * XS + i] = FMA(xh, sGam[i], sBet[i]);
+  }
+  if (live && l == 0) rstd_out[row] = rstd;
+  __syncthreads();
+  const float* __restrict__ u = sU + g * XS;
+  for (int o = l; o < Dout; o += L) {
+    const float* __restrict__ w = sW + o * XS;
+    float acc = sB[o];
+#pragma unroll 8
+    for (int i = 0; i < Din; ++i) acc = FMA(u[i], w[i], acc);
+    if (live) out[row * Dout + o] = acc > 0.f ? acc : 0.f;
+  }
+}
+
+// backward of the block's rows of one row class: gpre = gout*(out>0) and
+// gu = W^T gpre stored; with GIN the input grad through the LN backward.
+// NFU = leading fused terms of a gu chain, NTAIL = trailing gin elements
+// that take the rounded gh.
+template <int Din, int Dout, int NFU, int NTAIL, int L, bool GIN,
+          typename LoadG>
+__device__ __forceinline__ void rows_bwd_lanes(
+    const CachedPtrs& P, int w_slot, long r0, long nrows, LoadG loadg,
+    const float* __restrict__ out, const float* __restrict__ xhat,
+    const float* __restrict__ rst, float* __restrict__ gpre_store,
+    float* __restrict__ gu_store, float* __restrict__ gin) {
+  constexpr int RPB = ROW_NT / L;
+  constexpr int XS = Din + 1;
+  constexpr int GS = Dout + 1;
+  __shared__ float sGam[Din], sW[Dout * Din];
+  __shared__ float sG[RPB * GS], sGU[RPB * XS], sXH[GIN ? RPB * XS : 1];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Din; i += ROW_NT) sGam[i] = WP(w_slot)[i];
+  for (int x = tid; x < Dout * Din; x += ROW_NT) sW[x] = WP(w_slot + 2)[x];
+  for (int x = tid; x < RPB * Dout; x += ROW_NT) {
+    const int r = x / Dout, o = x % Dout;
+    const long row = r0 + r;
+    float gp = 0.f;
+    if (row < nrows) {
+      const float go = loadg(row, o);
+      gp = out[row * Dout + o] > 0.f ? go : 0.f;
+      gpre_store[row * Dout + o] = gp;
+    }
+    sG[r * GS + o] = gp;
+  }
+  if (GIN) {
+    for (int x = tid; x < RPB * Din; x += ROW_NT) {
+      const int r = x / Din, i = x % Din;
+      sXH[r * XS + i] = (r0 + r < nrows) ? xhat[(r0 + r) * Din + i] : 0.f;
+    }
+  }
+  __syncthreads();
+  const int g = tid / L, l = tid % L;
+  const long row = r0 + g;
+  const bool live = row < nrows;
+  const float* __restrict__ gp = sG + g * GS;
+  for (int i = l; i < Din; i += L) {
+    float acc = 0.f;
+#pragma unroll 8
+    for (int o = 0; o < Dout; ++o) {
+      if (o < NFU) acc = FMA(sW[o * Din + i], gp[o], acc);
+      else acc = acc + sW[o * Din + i] * gp[o];
+    }
+    if (live) gu_store[row * Din + i] = acc;
+    sGU[g * XS + i] = acc;
+  }
+  if (GIN) {
+    __syncthreads();
+    const float* __restrict__ gu = sGU + g * XS;
+    const float* __restrict__ xh = sXH + g * XS;
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll 8
+    for (int i = 0; i < Din; ++i) {
+      const float gh = gu[i] * sGam[i];
+      m1 = m1 + gh;
+      m2 = m2 + gh * xh[i];
+    }
+    const float m1d = m1 / Din;
+    const float m2d = m2 / Din;
+    const float rstd = live ? rst[row] : 0.f;
+    for (int i = l; i < Din; i += L) {
+      float a;
+      if (i < Din - NTAIL) a = FMA(gu[i], sGam[i], -m1d);
+      else a = FMA(m1, -1.f / Din, gu[i] * sGam[i]);
+      if (live) gin[row * Din + i] = rstd * FMA(-xh[i], m2d, a);
+    }
+  }
+}
+
+// Row classes never share a block: blocks [0, nb0) take the first class,
+// the rest the second, so a block runs one instantiation and its barriers
+// are block-uniform.
+template <int ROUND, int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_fwd_mlp_lanes_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int RPB = ROW_NT / L;
+  const int nbN = (D.N + RPB - 1) / RPB;
+  if ((int)blockIdx.x < nbN) {
+    const long r0 = (long)blockIdx.x * RPB;
+    if (ROUND == 1)
+      rows_fwd_lanes<KF0, KH, 1, L>(
+          P, W_LN_N1_W, r0, D.N,
+          [&](long v, int i) { return P.z0[v * KF0 + i]; },
+          P.xh_z1, P.rst_z1, P.hn1);
+    else
+      rows_fwd_lanes<KHID, KH, 0, L>(
+          P, W_LN_N2_W, r0, D.N,
+          [&](long v, int i) { return P.h1[v * KHID + i]; },
+          P.xh_h2, P.rst_h2, P.hn2);
+  } else {
+    const long r0 = (long)(blockIdx.x - nbN) * RPB;
+    auto ld = [&](long k, int i) { return P.e[k * KFE + i]; };
+    if (ROUND == 1)
+      rows_fwd_lanes<KFE, KH, 0, L>(P, W_LN_E1_W, r0, D.E, ld, P.xh_e1,
+                                    P.rst_e1, P.he1);
+    else
+      rows_fwd_lanes<KFE, KH, 0, L>(P, W_LN_E2_W, r0, D.E, ld, P.xh_e2,
+                                    P.rst_e2, P.he2);
+  }
+}
+
+template <int ROUND, int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_fwd_reduce_lanes_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int RPB = ROW_NT / L;
+  constexpr int DO = (ROUND == 1) ? KHID : KOUT;
+  constexpr int SLOT = (ROUND == 1) ? W_LN_R1_W : W_LN_R2_W;
+  const float* __restrict__ hn = (ROUND == 1) ? P.hn1 : P.hn2;
+  const float* __restrict__ he = (ROUND == 1) ? P.he1 : P.he2;
+  const int nbE = (D.E + RPB - 1) / RPB;
+  if ((int)blockIdx.x < nbE) {
+    const long r0 = (long)blockIdx.x * RPB;
+    rows_fwd_lanes<KMSG, DO, 0, L>(
+        P, SLOT, r0, D.E,
+        [&](long k, int i) {
+          return i < KH ? hn[P.src[k] * KH + i] : he[k * KH + (i - KH)];
+        },
+        (ROUND == 1) ? P.xh_m1e : P.xh_m2e,
+        (ROUND == 1) ? P.rst_m1e : P.rst_m2e,
+        (ROUND == 1) ? P.re1 : P.re2);
+  } else {
+    // self message = concat(hn[v], 0): the zero half's variance terms are
+    // the fused ones
+    const long r0 = (long)(blockIdx.x - nbE) * RPB;
+    rows_fwd_lanes<KMSG, DO, KH, L>(
+        P, SLOT, r0, D.N,
+        [&](long v, int i) { return i < KH ? hn[v * KH + i] : 0.f; },
+        (ROUND == 1) ? P.xh_m1s : P.xh_m2s,
+        (ROUND == 1) ? P.rst_m1s : P.rst_m2s,
+        (ROUND == 1) ? P.rs1 : P.rs2);
+  }
+}
+
+template <int ROUND, int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_bwd_reduce_lanes_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int RPB = ROW_NT / L;
+  constexpr int DO = (ROUND == 1) ? KHID : KOUT;
+  constexpr int SLOT = (ROUND == 1) ? W_LN_R1_W : W_LN_R2_W;
+  constexpr int NFU = DO - 12;
+  const float* __restrict__ gh = (ROUND == 1) ? P.gh1b : P.gh2;
+  const int nbE = (D.E + RPB - 1) / RPB;
+  if ((int)blockIdx.x < nbE) {
+    const long r0 = (long)blockIdx.x * RPB;
+    rows_bwd_lanes<KMSG, DO, NFU, 2, L, true>(
+        P, SLOT, r0, D.E,
+        [&](long k, int o) {
+          const int v = (int)P.dst[k];
+          const long deg = P.indptr[v + 1] - P.indptr[v];
+          const float f = 1.f / (float)(deg + 1);
+          return gh[(long)v * DO + o] * f;
+        },
+        (ROUND == 1) ? P.re1 : P.re2,
+        (ROUND == 1) ? P.xh_m1e : P.xh_m2e,
+        (ROUND == 1) ? P.rst_m1e : P.rst_m2e,
+        (ROUND == 1) ? P.gpre1_e : P.gpe2,
+        (ROUND == 1) ? P.gu_m1e : P.gu_m2e,
+        (ROUND == 1) ? P.gme1 : P.gme2);
+  } else {
+    const long r0 = (long)(blockIdx.x - nbE) * RPB;
+    rows_bwd_lanes<KMSG, DO, NFU, 2, L, true>(
+        P, SLOT, r0, D.N,
+        [&](long v, int o) {
+          const long deg = P.indptr[v + 1] - P.indptr[v];
+          const float f = (deg > 0) ? 1.f / (float)(deg + 1) : 0.f;
+          return gh[v * DO + o] * f;
+        },
+        (ROUND == 1) ? P.rs1 : P.rs2,
+        (ROUND == 1) ? P.xh_m1s : P.xh_m2s,
+        (ROUND == 1) ? P.rst_m1s : P.rst_m2s,
+        (ROUND == 1) ? P.gpre1_s : P.gpn2,
+        (ROUND == 1) ? P.gu_m1s : P.gu_m2s,
+        (ROUND == 1) ? P.gms1 : P.gms2);
+  }
+}
+
+template <int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_bwd_mlp2_lanes_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int RPB = ROW_NT / L;
+  const int nbN = (D.N + RPB - 1) / RPB;
+  if ((int)blockIdx.x < nbN) {
+    const long r0 = (long)blockIdx.x * RPB;
+    rows_bwd_lanes<KHID, KH, KH, 0, L, true>(
+        P, W_LN_N2_W, r0, D.N,
+        [&](long v, int o) { return P.ghn2[v * KH + o]; },
+        P.hn2, P.xh_h2, P.rst_h2, P.gpn1, P.gu_h2, P.gh1b);
+  } else {
+    const long r0 = (long)(blockIdx.x - nbN) * RPB;
+    rows_bwd_lanes<KFE, KH, KH, 0, L, false>(
+        P, W_LN_E2_W, r0, D.E,
+        [&](long k, int o) { return P.ghe2[k * KH + o]; },
+        P.he2, nullptr, nullptr, P.gpe1, P.gu_e2, nullptr);
+  }
+}
+
+// module-1 LN-out grad rows: one thread per gu element (all 16 terms fused)
+__global__ void __launch_bounds__(ROW_NT)
+cs_bwd_gu1_lanes_kernel(CachedPtrs P, CachedDims D) {
+  __shared__ float sWN[KH * KF0], sWE[KH * KFE];
+  const int tid = threadIdx.x;
+  for (int x = tid; x < KH * KF0; x += ROW_NT) sWN[x] = WP(W_N1_W)[x];
+  for (int x = tid; x < KH * KFE; x += ROW_NT) sWE[x] = WP(W_E1_W)[x];
+  __syncthreads();
+  const long nU = (long)D.N * KF0;
+  const long total = nU + (long)D.E * KFE;
+  const long u = (long)blockIdx.x * ROW_NT + tid;
+  if (u >= total) return;
+  if (u < nU) {
+    const long v = u / KF0;
+    const int i = (int)(u % KF0);
+    float acc = 0.f;
+#pragma unroll
+    for (int o = 0; o < KH; ++o)
+      acc = FMA(sWN[o * KF0 + i], P.ghn1[v * KH + o], acc);
+    P.gu_z1[u] = acc;
+  } else {
+    const long x = u - nU;
+    const long k = x / KFE;
+    const int i = (int)(x % KFE);
+    float acc = 0.f;
+#pragma unroll
+    for (int o = 0; o < KH; ++o)
+      acc = FMA(sWE[o * KFE + i], P.ghe1[k * KH + o], acc);
+    P.gu_e1[x] = acc;
+  }
+}
+
+// ===========================================================================
 // host bindings
 // ===========================================================================
 
-static void fill_ptrs(CachedPtrs& P, CachedDims& D,
+// Row-kernel selection, read per call like DDLS_AMD_WGRAD_MFMA:
+//   DDLS_AMD_ROW_KERNELS=thread  the thread-per-row kernels (oracle / A/B)
+//   DDLS_AMD_ROW_LANES=8|16|32   lanes per row for ALL lane-parallel kernels
+//                                (measurement switch).  Unset: each launch's
+//                                own default, the best of the three as
+//                                measured on MI355X at the benchmark's 417
+//                                rows (docs/KERNELS.md "Round 5"): 32 for the
+//                                two 32x64 reduce-module-1 kernels, else 16.
+struct RowCfg {
+  bool thread;
+  int lanes;   // 0: per-kernel default
+};
+
+static RowCfg row_cfg() {
+  RowCfg c;
+  const char* rk = getenv("DDLS_AMD_ROW_KERNELS");
+  c.thread = (rk != nullptr && strcmp(rk, "thread") == 0);
+  TORCH_CHECK(rk == nullptr || rk[0] == '\0' || c.thread
+              || strcmp(rk, "lanes") == 0,
+              "cached_step: DDLS_AMD_ROW_KERNELS must be 'thread' or "
+              "'lanes', got '", rk, "'");
+  c.lanes = 0;
+  const char* rl = getenv("DDLS_AMD_ROW_LANES");
+  if (rl != nullptr && rl[0] != '\0') {
+    c.lanes = atoi(rl);
+    TORCH_CHECK(c.lanes == 8 || c.lanes == 16 || c.lanes == 32,
+                "cached_step: DDLS_AMD_ROW_LANES must be 8, 16 or 32, got '",
+                rl, "'");
+  }
+  return c;
+}
+
+// launch KERNEL<..., L> for the configured group size (DEFL when not
+// configured) over the two row classes' blocks
+#define LAUNCH_ROWS(KERNEL_L, DEFL, rows0, rows1)                            \
+  do {                                                                       \
+    const int L_ = R.lanes ? R.lanes : (DEFL);                               \
+    const int rpb_ = ROW_NT / L_;                                            \
+    const int nb_ = ((rows0) + rpb_ - 1) / rpb_ + ((rows1) + rpb_ - 1) / rpb_; \
+    if (nb_ > 0) {                                                           \
+      if (L_ == 8)                                                           \
+        hipLaunchKernelGGL(KERNEL_L(8), dim3(nb_), dim3(ROW_NT), 0, stream,  \
+                           P, D);                                            \
+      else if (L_ == 16)                                                     \
+        hipLaunchKernelGGL(KERNEL_L(16), dim3(nb_), dim3(ROW_NT), 0, stream, \
+                           P, D);                                            \
+      else                                                                   \
+        hipLaunchKernelGGL(KERNEL_L(32), dim3(nb_), dim3(ROW_NT), 0, stream, \
+                           P, D);                                            \
+    }                                                                        \
+  } while (0)
+#define K_FWD_MLP1(L) (cs_fwd_mlp_lanes_kernel<1, L>)
+#define K_FWD_MLP2(L) (cs_fwd_mlp_lanes_kernel<2, L>)
+#define K_FWD_RED1(L) (cs_fwd_reduce_lanes_kernel<1, L>)
+#define K_FWD_RED2(L) (cs_fwd_reduce_lanes_kernel<2, L>)
+#define K_BWD_RED1(L) (cs_bwd_reduce_lanes_kernel<1, L>)
+#define K_BWD_RED2(L) (cs_bwd_reduce_lanes_kernel<2, L>)
+#define K_BWD_MLP2(L) (cs_bwd_mlp2_lanes_kernel<L>)
+
+static void fill_ptrs(CachedPtrs& P, CachedDims& D, RowCfg& R,
                       std::vector<torch::Tensor>& T,
                       std::vector<double>& fs) {
   TORCH_CHECK((int)T.size() == C_NT, "cached_step: tensor list size ",
@@ -1429,6 +1827,7 @@ static void fill_ptrs(CachedPtrs& P, CachedDims& D,
   D.FC = (int)T[C_H1P].size(1);
   const char* wm = getenv("DDLS_AMD_WGRAD_MFMA");
   D.wgrad_mfma = (wm != nullptr && wm[0] == '1') ? 1 : 0;
+  R = row_cfg();
   D.clip = (float)fs[0];
   D.vf_clip = (float)fs[1];
   D.vf_coef = (float)fs[2];
@@ -1534,21 +1933,32 @@ static void fill_ptrs(CachedPtrs& P, CachedDims& D,
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
   CachedPtrs P;
   CachedDims D;
-  fill_ptrs(P, D, T, fs);
+  RowCfg R;
+  fill_ptrs(P, D, R, T, fs);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   const int rows_b = (D.N + D.E + 255) / 256;
   const int comb1_b = ((long)D.N * D.HID + 255) / 256;
   const int comb2_b = ((long)D.N * D.OUT + 255) / 256;
-  hipLaunchKernelGGL(cs_fwd_mlp_kernel<1>, dim3(rows_b), dim3(256), 0,
-                     stream, P, D);
-  hipLaunchKernelGGL(cs_fwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
-                     stream, P, D);
+  if (R.thread) {
+    hipLaunchKernelGGL(cs_fwd_mlp_kernel<1>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+  } else {
+    LAUNCH_ROWS(K_FWD_MLP1, 16, D.N, D.E);
+    LAUNCH_ROWS(K_FWD_RED1, 32, D.E, D.N);
+  }
   hipLaunchKernelGGL(cs_fwd_combine_kernel<1>, dim3(comb1_b), dim3(256), 0,
                      stream, P, D);
-  hipLaunchKernelGGL(cs_fwd_mlp_kernel<2>, dim3(rows_b), dim3(256), 0,
-                     stream, P, D);
-  hipLaunchKernelGGL(cs_fwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
-                     stream, P, D);
+  if (R.thread) {
+    hipLaunchKernelGGL(cs_fwd_mlp_kernel<2>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+  } else {
+    LAUNCH_ROWS(K_FWD_MLP2, 16, D.N, D.E);
+    LAUNCH_ROWS(K_FWD_RED2, 16, D.E, D.N);
+  }
   hipLaunchKernelGGL(cs_fwd_combine_kernel<2>, dim3(comb2_b), dim3(256), 0,
                      stream, P, D);
   hipLaunchKernelGGL(cs_fwd_pool_kernel, dim3(1), dim3(512), 0, stream,
@@ -1566,7 +1976,8 @@ void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
 void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
   CachedPtrs P;
   CachedDims D;
-  fill_ptrs(P, D, T, fs);
+  RowCfg R;
+  fill_ptrs(P, D, R, T, fs);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   // cs_bwd_pool keeps the minibatch's model ids in a fixed LDS array
   TORCH_CHECK(D.B <= 1024, "cached_step: minibatch larger than 1024");
@@ -1577,18 +1988,34 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
                      P, D);
   hipLaunchKernelGGL(cs_bwd_pool_kernel, dim3(1), dim3(512), 0, stream,
                      P, D);
-  hipLaunchKernelGGL(cs_bwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
-                     stream, P, D);
+  if (R.thread)
+    hipLaunchKernelGGL(cs_bwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+  else
+    LAUNCH_ROWS(K_BWD_RED2, 16, D.E, D.N);
   hipLaunchKernelGGL(cs_bwd_scatter_kernel<2>, dim3(scat_b), dim3(256), 0,
                      stream, P, D);
-  hipLaunchKernelGGL(cs_bwd_mlp2_kernel, dim3(rows_b), dim3(256), 0, stream,
-                     P, D);
-  hipLaunchKernelGGL(cs_bwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
-                     stream, P, D);
+  if (R.thread) {
+    hipLaunchKernelGGL(cs_bwd_mlp2_kernel, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_bwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+  } else {
+    LAUNCH_ROWS(K_BWD_MLP2, 16, D.N, D.E);
+    LAUNCH_ROWS(K_BWD_RED1, 32, D.E, D.N);
+  }
   hipLaunchKernelGGL(cs_bwd_scatter_kernel<1>, dim3(scat_b), dim3(256), 0,
                      stream, P, D);
-  hipLaunchKernelGGL(cs_bwd_gu1_kernel, dim3(rows_b), dim3(256), 0, stream,
-                     P, D);
+  if (R.thread) {
+    hipLaunchKernelGGL(cs_bwd_gu1_kernel, dim3(rows_b), dim3(256), 0, stream,
+                       P, D);
+  } else {
+    const int gu1_b =
+        (int)(((long)D.N * KF0 + (long)D.E * KFE + ROW_NT - 1) / ROW_NT);
+    if (gu1_b > 0)
+      hipLaunchKernelGGL(cs_bwd_gu1_lanes_kernel, dim3(gu1_b), dim3(ROW_NT),
+                         0, stream, P, D);
+  }
   const int nsplit = D.wgrad_mfma ? 1 : WSPLIT;
   // 6 row jobs x nsplit, the graph-module block, 16 FC-column blocks
   hipLaunchKernelGGL(cs_bwd_w_kernel, dim3(6 * nsplit + 1 + 16), dim3(256),
