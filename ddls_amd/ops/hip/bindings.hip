@@ -41,6 +41,12 @@ void flat_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                torch::Tensor v, torch::Tensor step_t, torch::Tensor normsq,
                double clip, double lr, double b1, double b2, double eps);
 void flat_sumsq(torch::Tensor x, torch::Tensor out);
+void flat_sumsq_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                     torch::Tensor v, torch::Tensor step_t,
+                     torch::Tensor normsq, torch::Tensor partials,
+                     double clip, double lr, double b1, double b2,
+                     double eps);
+int64_t flat_sumsq_blocks(int64_t numel);
 std::vector<torch::Tensor> head_fwd(
     torch::Tensor gm, torch::Tensor gf, torch::Tensor mask,
     torch::Tensor ln_w, torch::Tensor ln_b, torch::Tensor Wg,
@@ -106,6 +112,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("message_reduce_bwd_mfma", &message_reduce_bwd_mfma,
           "matrix-core message-passing backward (3-stage MFMA)");
     m.def("flat_sumsq", &flat_sumsq, "capture-safe sum of squares");
+    m.def("flat_sumsq_adam", &flat_sumsq_adam,
+          "grad-norm partials + step count, then clip + Adam: the two-launch "
+          "optimiser tail of the captured step");
+    m.def("flat_sumsq_blocks", &flat_sumsq_blocks,
+          "number of partial sums flat_sumsq_adam writes for numel floats");
     m.def("head_fwd", &head_fwd,
           "fused policy/value head forward (LN+graphMLP+concat+2 branches)");
     m.def("head_bwd", &head_bwd, "fused policy/value head backward");

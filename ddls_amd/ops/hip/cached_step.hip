@@ -15,6 +15,29 @@
 //         cs_bwd_gnn   (1 WG)   pool grads + both MeanPool rounds' data bwd
 //         cs_bwd_w     (many)   ALL weight/bias/LN grads into flat_g
 //
+// That was the first cut.  The step is now 13 launches (16 per replay with
+// the stage kernel and the two-launch optimiser tail), in this order:
+//
+//   fwd:  cs_fwd_mlp_lanes<1>        round-1 node / edge modules
+//         cs_fwd_reduce_lanes<1>     round-1 reduce module (edge + self rows)
+//         cs_fwd_comb1_mlp2_lanes    h1 = CSR mean, then the round-2 modules
+//         cs_fwd_reduce_lanes<2>     round-2 reduce module
+//         cs_fwd_comb2_pool          h2 = CSR mean + per-model means
+//         cs_head                    per SAMPLE: final row, FC branches,
+//                                    logits/value, loss row, and the whole
+//                                    head backward down to gfinal / gu34
+//   bwd:  cs_bwd_pool                pool grads -> gh2
+//         cs_bwd_reduce_lanes<2>     round-2 reduce module backward
+//         cs_bwd_scat2_mlp2_lanes    scatter to ghn2/ghe2 + round-2 modules
+//         cs_bwd_reduce_lanes<1>     round-1 reduce module backward
+//         cs_bwd_scat1_gu1           scatter to ghn1/ghe1 + module-1 gu rows
+//                                    (+ one block for the C_STATS sums)
+//         cs_bwd_w, cs_bwd_w_reduce  all weight grads into flat_g
+//
+// DDLS_AMD_STEP_FUSION=off launches the previous 20 separate kernels and
+// DDLS_AMD_ROW_KERNELS=thread the thread-per-row ones before them; both
+// sets stay in this file unchanged as oracles for bitwise comparison.
+//
 // Exact-by-linearity gradient aggregation: per-sample dL/d emb reaches the
 // (shared) per-model GNN summed over the minibatch — the same contraction
 // index_select's backward performs, done here in one deterministic pass.
@@ -1743,6 +1766,548 @@ cs_bwd_gu1_lanes_kernel(CachedPtrs P, CachedDims D) {
 }
 
 // ===========================================================================
+// fused launches
+// ===========================================================================
+//
+// Neighbouring kernels whose dependencies are row-local or sample-local, run
+// as one launch each (a replay is a serial chain of launches, each near the
+// dispatch floor).  Default; DDLS_AMD_STEP_FUSION=off launches the separate
+// kernels above, which stay in the file unchanged as the oracle.  Every
+// tensor the separate kernels wrote is still written, in the same bits: the
+// summation orders are theirs, and the roundings are the ones their gfx950
+// ISA has (docs/KERNELS.md "Round 6"):
+//   fwd_head       bias first, i = 0..23, every term fused
+//   fwd_logits     16-term chunk partial: terms 0-3 fused onto 0, 4-15 rounded
+//                  products; logit = bias + partials c = 0..15, plain adds;
+//                  value = W2v*h1v rounded, 256-wide halving tree, + bias
+//   fwd_loss       plain adds for Z; entropy terms fused: fma(-lp, exp(lp), .)
+//   combine        plain adds in CSR order, IEEE division by deg+1
+//   scatter        plain adds in src-CSR order
+
+// ---- per-sample chain: fwd_head + fwd_logits + fwd_loss + bwd_head ----
+#define HD_HS 4                    // samples in flight per block
+#define HD_CS 20                   // LDS stride of a 16-float chunk: lanes
+                                   // that read one chunk each (b128) spread
+                                   // over all banks
+#define HD_ROW (16 * HD_CS)        // a KFC-wide row stored as 16 chunks
+__device__ __forceinline__ int hd_pad(int j) {
+  return (j >> 4) * HD_CS + (j & 15);
+}
+
+// Blocks and sample ranges are cs_bwd_head_kernel's: min(B, 32) blocks, each
+// walking its contiguous range HD_HS samples at a time.  Thread j owns hidden
+// unit j of both branches through the forward AND the backward (its W1p/W1v
+// rows sit in registers for the forward; h1p/h1v stay in registers as the
+// relu masks); rows that another thread needs go through LDS, and every row
+// the separate kernels stored is stored for cs_bwd_w and the tests.
+__global__ void __launch_bounds__(256)
+cs_head_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int HS = HD_HS;
+  __shared__ float sW2p[KA * HD_ROW];
+  __shared__ float sW1p[KFC * KFIN], sW1v[KFC * KFIN], sWg[KGE * KGF];
+  __shared__ float sB2p[KA];
+  // backward rows; +1 keeps the HS rows of one column on distinct banks
+  __shared__ float sGL[HS][KA], sGV[HS], sGF[HS][KFIN];
+  __shared__ float sGHp[HS][KFC + 1], sGHv[HS][KFC + 1];
+  // forward rows
+  __shared__ float sFin[HS][KFIN], sHp[HS][HD_ROW], sVred[HS][KFC];
+  __shared__ float sGf[HS][KGF], sU34[HS][KGF];
+  __shared__ float sGamG[KGF], sBetG[KGF], sBg[KGE];
+  __shared__ float sPart[HS][KA][16 + 1];
+  __shared__ float sRow[HS][KA], sPp[HS][KA], sLp[HS][KA];
+  __shared__ float sVal[HS], sCoef[HS], sHent[HS];
+  const int tid = threadIdx.x;
+  constexpr int NT = 256;
+  for (int x = tid; x < KA * KFC; x += NT)
+    sW2p[(x / KFC) * HD_ROW + hd_pad(x % KFC)] = WP(W_P2_W)[x];
+  for (int x = tid; x < KGE * KGF; x += NT) sWg[x] = WP(W_G_W)[x];
+  if (tid < KA) sB2p[tid] = WP(W_P2_B)[tid];
+  if (tid < KGF) {
+    sGamG[tid] = WP(W_LN_G_W)[tid];
+    sBetG[tid] = WP(W_LN_G_B)[tid];
+  }
+  if (tid < KGE) sBg[tid] = WP(W_G_B)[tid];
+  float w1p[KFIN], w1v[KFIN];
+#pragma unroll
+  for (int i = 0; i < KFIN; ++i) {
+    w1p[i] = WP(W_P1_W)[tid * KFIN + i];
+    w1v[i] = WP(W_V1_W)[tid * KFIN + i];
+  }
+  // the backward's LDS copy of W1p / W1v comes out of the same registers:
+  // the block's threads hold exactly the two matrices, one row each
+#pragma unroll
+  for (int i = 0; i < KFIN; ++i) {
+    sW1p[tid * KFIN + i] = w1p[i];
+    sW1v[tid * KFIN + i] = w1v[i];
+  }
+  const float b1p = WP(W_P1_B)[tid], b1v = WP(W_V1_B)[tid];
+  const float w2v = WP(W_V2_W)[tid];
+  const float b2v = WP(W_V2_B)[0];
+  const float klc = P.kl[0];
+  const int wv = tid >> 6, ln = tid & 63;
+  const int per = (D.B + gridDim.x - 1) / gridDim.x;
+  const int b0 = blockIdx.x * per;
+  const int b1 = min(D.B, b0 + per);
+  for (int c0 = b0; c0 < b1; c0 += HS) {
+    const int ns = min(HS, b1 - c0);
+    // final = concat(pooled[model], graph_module(LN(gf))): the per-sample
+    // half of cs_fwd_pool_kernel.  The lanes of a sample walk its gf row
+    // redundantly for the LN sums (same bits in every lane).
+    for (int x = tid; x < ns * KGF; x += NT)
+      sGf[x / KGF][x % KGF] = P.gf[(long)c0 * KGF + x];
+    for (int x = tid; x < ns * KOUT; x += NT) {
+      const int s = x / KOUT, i = x % KOUT;
+      const long mid = P.model_ids[c0 + s];
+      const float pv = P.pooled[mid * KOUT + i];
+      sFin[s][i] = pv;
+      P.fin[(long)(c0 + s) * KFIN + i] = pv;
+    }
+    __syncthreads();
+    for (int x = tid; x < ns * KGF; x += NT) {
+      const int s = x / KGF, i = x % KGF;
+      const float* __restrict__ xr = sGf[s];
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < KGF; ++k) sum = sum + xr[k];
+      const float mu = sum / KGF;
+      float var;
+      {
+        const float d0 = xr[0] - mu;
+        var = d0 * d0;
+      }
+#pragma unroll
+      for (int k = 1; k < KGF; ++k) {
+        const float d = xr[k] - mu;
+        var = var + d * d;
+      }
+      const float rstd = rsqrtf(var / KGF + LN_EPS);
+      const float xh = (xr[i] - mu) * rstd;
+      P.xh34[(long)(c0 + s) * KGF + i] = xh;
+      sU34[s][i] = FMA(xh, sGamG[i], sBetG[i]);
+    }
+    __syncthreads();
+    for (int x = tid; x < ns * KGE; x += NT) {
+      const int s = x / KGE, o = x % KGE;
+      float acc = sBg[o];
+#pragma unroll
+      for (int i = 0; i < KGF; ++i)
+        acc = FMA(sWg[o * KGF + i], sU34[s][i], acc);
+      sFin[s][KOUT + o] = acc;               // graph_module has NO activation
+      P.fin[(long)(c0 + s) * KFIN + KOUT + o] = acc;
+    }
+    __syncthreads();
+    // FC hidden layers: bias first, i ascending
+    float hp[HS], hv[HS];
+#pragma unroll
+    for (int s = 0; s < HS; ++s) {
+      hp[s] = 0.f;
+      hv[s] = 0.f;
+      if (s < ns) {
+        float ap = b1p, av = b1v;
+#pragma unroll
+        for (int i = 0; i < KFIN; ++i) {
+          ap = FMA(w1p[i], sFin[s][i], ap);
+          av = FMA(w1v[i], sFin[s][i], av);
+        }
+        ap = ap > 0.f ? ap : 0.f;
+        av = av > 0.f ? av : 0.f;
+        const long u = (long)(c0 + s) * KFC + tid;
+        P.h1p[u] = ap;
+        P.h1v[u] = av;
+        hp[s] = ap;
+        hv[s] = av;
+        sHp[s][hd_pad(tid)] = ap;
+        sVred[s][tid] = w2v * av;
+      }
+    }
+    __syncthreads();
+    // logit partials over the 16 chunks of the hidden row
+    for (int x = tid; x < ns * KA * 16; x += NT) {
+      const int s = x / (KA * 16), r = x % (KA * 16);
+      const int a = r / 16, c = r % 16;
+      const float* __restrict__ w = sW2p + a * HD_ROW + c * HD_CS;
+      const float* __restrict__ h = sHp[s] + c * HD_CS;
+      float acc = FMA(w[0], h[0], 0.f);
+#pragma unroll
+      for (int i = 1; i < 16; ++i) {
+        if (i < 4) acc = FMA(w[i], h[i], acc);
+        else acc = acc + w[i] * h[i];
+      }
+      sPart[s][a][c] = acc;
+    }
+    // value: wave s folds sample s's 256 products in the halving tree's
+    // pairing (t with t + 128, 64, ... 1)
+    if (wv < ns) {
+      const float* __restrict__ vr = sVred[wv];
+      float a0 = vr[ln] + vr[ln + 128];
+      const float a1 = vr[ln + 64] + vr[ln + 192];
+      a0 = a0 + a1;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1)
+        a0 = a0 + __shfl_down(a0, off, 64);
+      if (ln == 0) {
+        const float val = a0 + b2v;
+        sVal[wv] = val;
+        P.values[c0 + wv] = val;
+      }
+    }
+    __syncthreads();
+    // raw masked logits
+    for (int x = tid; x < ns * KA; x += NT) {
+      const int s = x / KA, a = x % KA;
+      float acc = sB2p[a];
+#pragma unroll
+      for (int c = 0; c < 16; ++c) acc = acc + sPart[s][a][c];
+      const float fmin = -3.402823466e+38f;
+      float lm = logf(P.mask[(long)c0 * KA + x]);
+      if (!(lm > fmin)) lm = fmin;
+      sRow[s][a] = acc + lm;
+    }
+    __syncthreads();
+    // softmax / surrogate row of sample s: lane 0 of wave s
+    if (wv < ns && ln == 0) {
+      const int s = wv;
+      const int b = c0 + s;
+      const float* __restrict__ row = sRow[s];
+      float mx = -3.0e38f;
+#pragma unroll
+      for (int a = 0; a < KA; ++a) mx = fmaxf(mx, row[a]);
+      float Z = 0.f;
+#pragma unroll
+      for (int a = 0; a < KA; ++a) Z = Z + __expf(row[a] - mx);
+      const float lse = mx + __logf(Z);
+      float ent = 0.f;
+#pragma unroll
+      for (int a = 0; a < KA; ++a) {
+        const float lp = row[a] - lse;
+        const float e = __expf(lp);
+        sLp[s][a] = lp;
+        sPp[s][a] = e;
+        ent = FMA(-lp, e, ent);
+      }
+      const long act = P.actions[b];
+      const float logp_a = sLp[s][act];
+      const float old_lp = P.old_logp[b];
+      const float ratio = __expf(logp_a - old_lp);
+      const float A_b = P.adv[b];
+      const float r_cl = fminf(fmaxf(ratio, 1.f - D.clip), 1.f + D.clip);
+      const float surr1 = ratio * A_b, surr2 = r_cl * A_b;
+      float ds = ratio * A_b;
+      if (surr2 < surr1 && (ratio < 1.f - D.clip || ratio > 1.f + D.clip))
+        ds = 0.f;
+      const float coef = -ds - klc;
+      P.hent[b] = ent;
+      P.coef[b] = coef;
+      sHent[s] = ent;
+      sCoef[s] = coef;
+    }
+    __syncthreads();
+    // loss backward rows (upstream grad = 1); p and lp go out here
+    for (int x = tid; x < ns * KA; x += NT) {
+      const int s = x / KA, a = x % KA;
+      const int b = c0 + s;
+      const long u = (long)b * KA + a;
+      const long act = P.actions[b];
+      const float c = sCoef[s] / D.B;
+      const float pj = sPp[s][a];
+      const float lpj = sLp[s][a];
+      P.p[u] = pj;
+      P.lp[u] = lpj;
+      const float delta = (a == (int)act) ? 1.f : 0.f;
+      const float gl = mul_rn(c, delta - pj)
+                       + mul_rn(mul_rn(D.ent_coef / D.B, pj),
+                                lpj + sHent[s]);
+      P.glogits[u] = gl;
+      sGL[s][a] = gl;
+    }
+    if (tid >= 128 && tid < 128 + ns) {
+      const int s = tid - 128;
+      const int b = c0 + s;
+      const float verr = sVal[s] - P.vtarg[b];
+      const float mk = (verr * verr <= D.vf_clip) ? 1.f : 0.f;
+      const float gv = D.vf_coef * 2.f * verr * mk / D.B;
+      P.gvalue[b] = gv;
+      sGV[s] = gv;
+    }
+    __syncthreads();
+    // hidden grads
+#pragma unroll
+    for (int s = 0; s < HS; ++s) {
+      if (s < ns) {
+        const int j = tid;
+        const long u = (long)(c0 + s) * KFC + j;
+        float acc = 0.f;
+#pragma unroll
+        for (int a = 0; a < KA; ++a) {
+          // the first five terms are fused, the rest rounded products
+          const float w = sW2p[a * HD_ROW + hd_pad(j)];
+          if (a < 5) acc = FMA(w, sGL[s][a], acc);
+          else acc = acc + mul_rn(w, sGL[s][a]);
+        }
+        const float gp = hp[s] > 0.f ? acc : 0.f;
+        const float av = w2v * sGV[s];
+        const float gv = hv[s] > 0.f ? av : 0.f;
+        P.gh1p[u] = gp;
+        P.gh1v[u] = gv;
+        sGHp[s][j] = gp;
+        sGHv[s][j] = gv;
+      }
+    }
+    __syncthreads();
+    // gfinal: one thread per (sample, i), j = 0..FC-1 in order
+    for (int x = tid; x < ns * KFIN; x += NT) {
+      const int s = x / KFIN, i = x % KFIN;
+      float acc = 0.f;
+#pragma unroll 8
+      for (int j = 0; j < KFC; ++j) {
+        acc = FMA(sW1p[j * KFIN + i], sGHp[s][j], acc);
+        acc = FMA(sW1v[j * KFIN + i], sGHv[s][j], acc);
+      }
+      P.gfinal[(long)(c0 + s) * KFIN + i] = acc;
+      sGF[s][i] = acc;
+    }
+    __syncthreads();
+    // graph-module LN-out grads
+    for (int x = tid; x < ns * KGF; x += NT) {
+      const int s = x / KGF, i = x % KGF;
+      float acc = 0.f;
+#pragma unroll
+      for (int o = 0; o < KGE; ++o)
+        acc = acc + mul_rn(sWg[o * KGF + i], sGF[s][KOUT + o]);
+      P.gu34[(long)(c0 + s) * KGF + i] = acc;
+    }
+    // no barrier here: every row buffer's next write is at least one
+    // barrier after its last read above
+  }
+  // the logging-only C_STATS sums are taken from the stored rows by the
+  // statistics blocks of cs_bwd_scat1_gu1_kernel
+}
+
+// ---- cs_fwd_combine<2> + the per-model means of cs_fwd_pool ----
+// One block per model: its nodes' h2 rows are computed into the LDS tile
+// (and written out), then unit i adds them in node order, as a chain out of
+// LDS.  The per-sample half of cs_fwd_pool_kernel is in cs_head_kernel.
+__global__ void __launch_bounds__(256)
+cs_fwd_comb2_pool_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int PT = 256;   // node rows of h2 per tile
+  __shared__ float sH2[PT * KOUT];
+  const int tid = threadIdx.x;
+  const int m = blockIdx.x;
+  const long lo = P.model_nptr[m], hi = P.model_nptr[m + 1];
+  float acc = 0.f;
+  for (long v0 = lo; v0 < hi; v0 += PT) {
+    const long v1 = min(hi, v0 + PT);
+    __syncthreads();
+    for (long x = tid; x < (v1 - v0) * KOUT; x += 256) {
+      const long v = v0 + x / KOUT;
+      const int i = (int)(x % KOUT);
+      const long qlo = P.indptr[v], qhi = P.indptr[v + 1];
+      float out = 0.f;
+      if (qhi > qlo) {
+        float a = P.rs2[v * KOUT + i];
+        for (long q = qlo; q < qhi; ++q)
+          a = a + P.re2[P.order[q] * KOUT + i];
+        out = a / (float)(qhi - qlo + 1);
+      }
+      P.h2[v * KOUT + i] = out;
+      sH2[x] = out;
+    }
+    __syncthreads();
+    if (tid < KOUT)
+      for (long v = v0; v < v1; ++v) acc = acc + sH2[(v - v0) * KOUT + tid];
+  }
+  if (tid < KOUT) P.pooled[(long)m * KOUT + tid] = acc / (float)(hi - lo);
+}
+
+// ---- cs_fwd_combine<1> inside cs_fwd_mlp_lanes<2>'s staging loop ----
+// The node rows of the block are h1 rows: each staged element is computed
+// here, (rs1[v] + sum over the in-edges in CSR order of re1) / (deg + 1),
+// 0 without in-edges, and written to h1 for the backward.
+template <int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_fwd_comb1_mlp2_lanes_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int RPB = ROW_NT / L;
+  const int nbN = (D.N + RPB - 1) / RPB;
+  if ((int)blockIdx.x < nbN) {
+    const long r0 = (long)blockIdx.x * RPB;
+    rows_fwd_lanes<KHID, KH, 0, L>(
+        P, W_LN_N2_W, r0, D.N,
+        [&](long v, int i) {
+          const long lo = P.indptr[v], hi = P.indptr[v + 1];
+          float out = 0.f;
+          if (hi > lo) {
+            float acc = P.rs1[v * KHID + i];
+            for (long q = lo; q < hi; ++q)
+              acc = acc + P.re1[P.order[q] * KHID + i];
+            out = acc / (float)(hi - lo + 1);
+          }
+          P.h1[v * KHID + i] = out;
+          return out;
+        },
+        P.xh_h2, P.rst_h2, P.hn2);
+  } else {
+    const long r0 = (long)(blockIdx.x - nbN) * RPB;
+    rows_fwd_lanes<KFE, KH, 0, L>(
+        P, W_LN_E2_W, r0, D.E,
+        [&](long k, int i) { return P.e[k * KFE + i]; },
+        P.xh_e2, P.rst_e2, P.he2);
+  }
+}
+
+// ---- cs_bwd_scatter<2> inside cs_bwd_mlp2_lanes's staging loop ----
+// ghn2[v] = gms2[v][:KH] + sum over the out-edges in src-CSR order of
+// gme2[.][:KH]; ghe2[k] = gme2[k][KH:].  Both are still written out.
+template <int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_bwd_scat2_mlp2_lanes_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int RPB = ROW_NT / L;
+  const int nbN = (D.N + RPB - 1) / RPB;
+  if ((int)blockIdx.x < nbN) {
+    const long r0 = (long)blockIdx.x * RPB;
+    rows_bwd_lanes<KHID, KH, KH, 0, L, true>(
+        P, W_LN_N2_W, r0, D.N,
+        [&](long v, int o) {
+          const long lo = P.src_indptr[v], hi = P.src_indptr[v + 1];
+          float acc = P.gms2[v * KMSG + o];
+          for (long q = lo; q < hi; ++q)
+            acc = acc + P.gme2[P.src_order[q] * KMSG + o];
+          P.ghn2[v * KH + o] = acc;
+          return acc;
+        },
+        P.hn2, P.xh_h2, P.rst_h2, P.gpn1, P.gu_h2, P.gh1b);
+  } else {
+    const long r0 = (long)(blockIdx.x - nbN) * RPB;
+    rows_bwd_lanes<KFE, KH, KH, 0, L, false>(
+        P, W_LN_E2_W, r0, D.E,
+        [&](long k, int o) {
+          const float g = P.gme2[k * KMSG + KH + o];
+          P.ghe2[k * KH + o] = g;
+          return g;
+        },
+        P.he2, nullptr, nullptr, P.gpe1, P.gu_e2, nullptr);
+  }
+}
+
+// ---- cs_bwd_scatter<1> + cs_bwd_gu1 ----
+// A block owns SG_RPB rows of one class (node blocks first, then edge
+// blocks): thread (r, i) scatters element i of row r with the relu mask,
+// the row stays in LDS, then one thread per gu element runs the 16-term
+// chain (all fused, from 0, o ascending).
+//
+// The grid's last block takes the C_STATS sums (logging only), which
+// cs_head_kernel leaves out.  It recomputes cs_fwd_loss_kernel's four terms
+// per sample from the stored rows (lp, values, hent: the same single
+// operations, so the same bits), sums them per group of 32 samples in sample
+// order, as that kernel's blocks do in LDS, and one thread adds the group
+// partials to C_STATS with float atomics in group order: the result
+// cs_fwd_loss_kernel gives when its blocks' atomics arrive in block order,
+// and the same bits on every run.
+#define SG_RPB (ROW_NT / KH)
+#define SG_SPB 32     // samples per statistics group
+#define SG_MAXB 1024  // cached_step_bwd refuses larger minibatches
+__global__ void __launch_bounds__(ROW_NT)
+cs_bwd_scat1_gu1_kernel(CachedPtrs P, CachedDims D) {
+  __shared__ float sWN[KH * KF0], sWE[KH * KFE];
+  __shared__ float sG[SG_RPB][KH + 1];
+  const int tid = threadIdx.x;
+  for (int x = tid; x < KH * KF0; x += ROW_NT) sWN[x] = WP(W_N1_W)[x];
+  for (int x = tid; x < KH * KFE; x += ROW_NT) sWE[x] = WP(W_E1_W)[x];
+  const int nbN = (D.N + SG_RPB - 1) / SG_RPB;
+  const int nbE = (D.E + SG_RPB - 1) / SG_RPB;
+  const int r = tid / KH, i = tid % KH;
+  if ((int)blockIdx.x >= nbN + nbE) {
+    __shared__ float sT[SG_MAXB][4];
+    __shared__ float sAcc[SG_MAXB / SG_SPB][4];
+    for (int b = tid; b < D.B; b += ROW_NT) {
+      const float logp_a = P.lp[(long)b * KA + P.actions[b]];
+      const float old_lp = P.old_logp[b];
+      const float ratio = __expf(logp_a - old_lp);
+      const float A_b = P.adv[b];
+      const float r_cl = fminf(fmaxf(ratio, 1.f - D.clip), 1.f + D.clip);
+      const float surr1 = ratio * A_b, surr2 = r_cl * A_b;
+      const float verr = P.values[b] - P.vtarg[b];
+      sT[b][0] = -fminf(surr1, surr2);
+      sT[b][1] = fminf(verr * verr, D.vf_clip);
+      sT[b][2] = old_lp - logp_a;
+      sT[b][3] = P.hent[b];
+    }
+    __syncthreads();
+    const int ng = (D.B + SG_SPB - 1) / SG_SPB;
+    // thread (g, k): statistic k of group g, samples in order
+    for (int x = tid; x < ng * 4; x += ROW_NT) {
+      const int g = x / 4, k = x % 4;
+      const int b_lo = g * SG_SPB;
+      const int nb = min(D.B - b_lo, SG_SPB);
+      float acc = sT[b_lo][k];
+      for (int t = 1; t < nb; ++t) acc = acc + sT[b_lo + t][k];
+      sAcc[g][k] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const float inv = 1.f / D.B;
+      const float klc = P.kl[0];
+      for (int g = 0; g < ng; ++g) {
+        const float pl = sAcc[g][0] * inv;
+        const float vf = sAcc[g][1] * inv;
+        const float kl = sAcc[g][2] * inv;
+        const float ent = sAcc[g][3] * inv;
+        atomicAdd(&P.stats[0], pl);
+        atomicAdd(&P.stats[1], vf);
+        atomicAdd(&P.stats[2], kl);
+        atomicAdd(&P.stats[3], ent);
+        atomicAdd(&P.stats[4],
+                  FMA(-D.ent_coef, ent, FMA(D.vf_coef, vf, FMA(kl, klc, pl))));
+      }
+    }
+  } else if ((int)blockIdx.x < nbN) {
+    const long r0 = (long)blockIdx.x * SG_RPB;
+    const long v = r0 + r;
+    float g = 0.f;
+    if (v < D.N) {
+      const long lo = P.src_indptr[v], hi = P.src_indptr[v + 1];
+      float acc = P.gms1[v * KMSG + i];
+      for (long q = lo; q < hi; ++q)
+        acc = acc + P.gme1[P.src_order[q] * KMSG + i];
+      g = P.hn1[v * KH + i] > 0.f ? acc : 0.f;
+      P.ghn1[v * KH + i] = g;
+    }
+    sG[r][i] = g;
+    __syncthreads();
+    for (int x = tid; x < SG_RPB * KF0; x += ROW_NT) {
+      const int rr = x / KF0, ii = x % KF0;
+      if (r0 + rr < D.N) {
+        float acc = 0.f;
+#pragma unroll
+        for (int o = 0; o < KH; ++o)
+          acc = FMA(sWN[o * KF0 + ii], sG[rr][o], acc);
+        P.gu_z1[(r0 + rr) * KF0 + ii] = acc;
+      }
+    }
+  } else {
+    const long r0 = (long)(blockIdx.x - nbN) * SG_RPB;
+    const long k = r0 + r;
+    float g = 0.f;
+    if (k < D.E) {
+      const float ge = P.gme1[k * KMSG + KH + i];
+      g = P.he1[k * KH + i] > 0.f ? ge : 0.f;
+      P.ghe1[k * KH + i] = g;
+    }
+    sG[r][i] = g;
+    __syncthreads();
+    for (int x = tid; x < SG_RPB * KFE; x += ROW_NT) {
+      const int rr = x / KFE, ii = x % KFE;
+      if (r0 + rr < D.E) {
+        float acc = 0.f;
+#pragma unroll
+        for (int o = 0; o < KH; ++o)
+          acc = FMA(sWE[o * KFE + ii], sG[rr][o], acc);
+        P.gu_e1[(r0 + rr) * KFE + ii] = acc;
+      }
+    }
+  }
+}
+
+// ===========================================================================
 // host bindings
 // ===========================================================================
 
@@ -1754,9 +2319,12 @@ cs_bwd_gu1_lanes_kernel(CachedPtrs P, CachedDims D) {
 //                                measured on MI355X at the benchmark's 417
 //                                rows (docs/KERNELS.md "Round 5"): 32 for the
 //                                two 32x64 reduce-module-1 kernels, else 16.
+//   DDLS_AMD_STEP_FUSION=off     the separate kernels of every fused launch
+//                                (oracle / A/B); 'thread' above implies it
 struct RowCfg {
   bool thread;
   int lanes;   // 0: per-kernel default
+  bool fused;  // the fused launches (needs the lane-parallel row kernels)
 };
 
 static RowCfg row_cfg() {
@@ -1775,6 +2343,12 @@ static RowCfg row_cfg() {
                 "cached_step: DDLS_AMD_ROW_LANES must be 8, 16 or 32, got '",
                 rl, "'");
   }
+  const char* sf = getenv("DDLS_AMD_STEP_FUSION");
+  const bool off = (sf != nullptr && strcmp(sf, "off") == 0);
+  TORCH_CHECK(sf == nullptr || sf[0] == '\0' || off || strcmp(sf, "on") == 0,
+              "cached_step: DDLS_AMD_STEP_FUSION must be 'on' or 'off', got '",
+              sf, "'");
+  c.fused = !off && !c.thread;
   return c;
 }
 
@@ -1804,6 +2378,8 @@ static RowCfg row_cfg() {
 #define K_BWD_RED1(L) (cs_bwd_reduce_lanes_kernel<1, L>)
 #define K_BWD_RED2(L) (cs_bwd_reduce_lanes_kernel<2, L>)
 #define K_BWD_MLP2(L) (cs_bwd_mlp2_lanes_kernel<L>)
+#define K_FWD_COMB1_MLP2(L) (cs_fwd_comb1_mlp2_lanes_kernel<L>)
+#define K_BWD_SCAT2_MLP2(L) (cs_bwd_scat2_mlp2_lanes_kernel<L>)
 
 static void fill_ptrs(CachedPtrs& P, CachedDims& D, RowCfg& R,
                       std::vector<torch::Tensor>& T,
@@ -1948,16 +2524,33 @@ void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
     LAUNCH_ROWS(K_FWD_MLP1, 16, D.N, D.E);
     LAUNCH_ROWS(K_FWD_RED1, 32, D.E, D.N);
   }
-  hipLaunchKernelGGL(cs_fwd_combine_kernel<1>, dim3(comb1_b), dim3(256), 0,
-                     stream, P, D);
+  if (!R.fused)
+    hipLaunchKernelGGL(cs_fwd_combine_kernel<1>, dim3(comb1_b), dim3(256), 0,
+                       stream, P, D);
   if (R.thread) {
     hipLaunchKernelGGL(cs_fwd_mlp_kernel<2>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
     hipLaunchKernelGGL(cs_fwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
   } else {
-    LAUNCH_ROWS(K_FWD_MLP2, 16, D.N, D.E);
+    if (R.fused)
+      LAUNCH_ROWS(K_FWD_COMB1_MLP2, 16, D.N, D.E);
+    else
+      LAUNCH_ROWS(K_FWD_MLP2, 16, D.N, D.E);
     LAUNCH_ROWS(K_FWD_RED2, 16, D.E, D.N);
+  }
+  if (R.fused) {
+    // h2 and the per-model means, one block per model; then the whole
+    // per-sample chain (final rows, head, loss, head backward) in one
+    // launch: cached_step_bwd starts at cs_bwd_pool
+    if (D.M > 0)
+      hipLaunchKernelGGL(cs_fwd_comb2_pool_kernel, dim3(D.M), dim3(256), 0,
+                         stream, P, D);
+    const int hb = D.B < 32 ? D.B : 32;
+    if (hb > 0)
+      hipLaunchKernelGGL(cs_head_kernel, dim3(hb), dim3(256), 0, stream,
+                         P, D);
+    return;
   }
   hipLaunchKernelGGL(cs_fwd_combine_kernel<2>, dim3(comb2_b), dim3(256), 0,
                      stream, P, D);
@@ -1980,12 +2573,14 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
   fill_ptrs(P, D, R, T, fs);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   // cs_bwd_pool keeps the minibatch's model ids in a fixed LDS array
-  TORCH_CHECK(D.B <= 1024, "cached_step: minibatch larger than 1024");
+  TORCH_CHECK(D.B <= 1024 && D.B <= SG_MAXB,
+              "cached_step: minibatch larger than 1024");
   int hb = D.B < 32 ? D.B : 32;
   const int rows_b = (D.N + D.E + 255) / 256;
   const int scat_b = ((long)(D.N + D.E) * D.H + 255) / 256;
-  hipLaunchKernelGGL(cs_bwd_head_kernel, dim3(hb), dim3(256), 0, stream,
-                     P, D);
+  if (!R.fused)
+    hipLaunchKernelGGL(cs_bwd_head_kernel, dim3(hb), dim3(256), 0, stream,
+                       P, D);
   hipLaunchKernelGGL(cs_bwd_pool_kernel, dim3(1), dim3(512), 0, stream,
                      P, D);
   if (R.thread)
@@ -1993,20 +2588,35 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
                        stream, P, D);
   else
     LAUNCH_ROWS(K_BWD_RED2, 16, D.E, D.N);
-  hipLaunchKernelGGL(cs_bwd_scatter_kernel<2>, dim3(scat_b), dim3(256), 0,
-                     stream, P, D);
+  if (!R.fused)
+    hipLaunchKernelGGL(cs_bwd_scatter_kernel<2>, dim3(scat_b), dim3(256), 0,
+                       stream, P, D);
   if (R.thread) {
     hipLaunchKernelGGL(cs_bwd_mlp2_kernel, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
     hipLaunchKernelGGL(cs_bwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
   } else {
-    LAUNCH_ROWS(K_BWD_MLP2, 16, D.N, D.E);
+    if (R.fused)
+      LAUNCH_ROWS(K_BWD_SCAT2_MLP2, 16, D.N, D.E);
+    else
+      LAUNCH_ROWS(K_BWD_MLP2, 16, D.N, D.E);
     LAUNCH_ROWS(K_BWD_RED1, 32, D.E, D.N);
   }
-  hipLaunchKernelGGL(cs_bwd_scatter_kernel<1>, dim3(scat_b), dim3(256), 0,
-                     stream, P, D);
-  if (R.thread) {
+  if (R.fused) {
+    // row blocks, then the loss-statistics block
+    const int sg_b = (D.N + SG_RPB - 1) / SG_RPB + (D.E + SG_RPB - 1) / SG_RPB
+                     + 1;
+    if (D.B > 0)
+      hipLaunchKernelGGL(cs_bwd_scat1_gu1_kernel, dim3(sg_b), dim3(ROW_NT),
+                         0, stream, P, D);
+  } else {
+    hipLaunchKernelGGL(cs_bwd_scatter_kernel<1>, dim3(scat_b), dim3(256), 0,
+                       stream, P, D);
+  }
+  if (R.fused) {
+    // gu_z1 / gu_e1 came out of the scatter launch above
+  } else if (R.thread) {
     hipLaunchKernelGGL(cs_bwd_gu1_kernel, dim3(rows_b), dim3(256), 0, stream,
                        P, D);
   } else {

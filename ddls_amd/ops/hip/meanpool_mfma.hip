@@ -688,3 +688,118 @@ void flat_sumsq(torch::Tensor x, torch::Tensor out) {
     hipLaunchKernelGGL(sumsq_kernel, dim3((int)blocks), dim3(BLOCK), 0,
                        stream, x.data_ptr<float>(), out.data_ptr<float>(), n);
 }
+
+// ---------------------------------------------------------------------------
+// Two-launch optimiser tail of the captured step (flat_sumsq + flat_adam are
+// four: zero1, sumsq, step_inc, flat_adam).
+//   K1 sumsq_partials: sumsq_kernel's grid and per-block reduction, but each
+//      block STORES its partial (no atomic, so nothing to zero first); block
+//      0 also advances step_t (the former step_inc).
+//   K2 flat_adam_partials: every block adds the partials from 0 in block
+//      order — one of the orders the float atomics of sumsq_kernel can
+//      produce, and the same one on every run — and then runs
+//      flat_adam_kernel's loop.  Block 0 publishes the sum in normsq[0].
+#define SUMSQ_MAX_BLOCKS 512
+
+__global__ void __launch_bounds__(BLOCK)
+sumsq_partials_kernel(const float* __restrict__ x,
+                      float* __restrict__ partials, float* step_t, long n) {
+    __shared__ float part[WAVES_PER_BLOCK];
+    const int wave = threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    float s = 0.0f;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n;
+         i += (long)gridDim.x * BLOCK)
+        s += x[i] * x[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        s += __shfl_down(s, off, WAVE);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+        for (int w = 0; w < WAVES_PER_BLOCK; ++w) t += part[w];
+        partials[blockIdx.x] = t;
+        if (blockIdx.x == 0) step_t[0] += 1.0f;
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK)
+flat_adam_partials_kernel(float* __restrict__ p, float* __restrict__ g,
+                          float* __restrict__ m, float* __restrict__ v,
+                          const float* __restrict__ step_t,    // [1]
+                          const float* __restrict__ partials,  // [nparts]
+                          float* __restrict__ normsq,          // [1]
+                          int nparts, long numel, float clip, float lr,
+                          float b1, float b2, float eps) {
+    __shared__ float sp[SUMSQ_MAX_BLOCKS];
+    __shared__ float ssum;
+    for (int k = threadIdx.x; k < nparts; k += BLOCK) sp[k] = partials[k];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+#pragma unroll 8
+        for (int k = 0; k < nparts; ++k) t += sp[k];
+        ssum = t;
+        if (blockIdx.x == 0) normsq[0] = t;
+    }
+    __syncthreads();
+    const float t = step_t[0];
+    float scale = 1.0f;
+    if (clip > 0.0f) {
+        const float norm = sqrtf(ssum);
+        const float c = clip / (norm + 1e-6f);
+        scale = fminf(c, 1.0f);
+    }
+    const float bias1 = 1.0f - powf(b1, t);
+    const float bias2 = 1.0f - powf(b2, t);
+    const float step_size = lr / bias1;
+    const float inv_sqrt_bias2 = rsqrtf(bias2);
+    const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < numel; i += stride) {
+        const float gi = g[i] * scale;
+        const float mi = b1 * m[i] + (1.0f - b1) * gi;
+        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] -= step_size * mi / (sqrtf(vi) * inv_sqrt_bias2 + eps);
+        g[i] = 0.0f;
+    }
+}
+
+void flat_sumsq_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                     torch::Tensor v, torch::Tensor step_t,
+                     torch::Tensor normsq, torch::Tensor partials,
+                     double clip, double lr, double b1, double b2,
+                     double eps) {
+    const long numel = p.numel();
+    TORCH_CHECK(g.numel() == numel && m.numel() == numel
+                && v.numel() == numel, "flat_sumsq_adam: size mismatch");
+    long sblocks = (numel + BLOCK - 1) / BLOCK;
+    if (sblocks > SUMSQ_MAX_BLOCKS) sblocks = SUMSQ_MAX_BLOCKS;
+    TORCH_CHECK(partials.numel() >= sblocks,
+                "flat_sumsq_adam: partials buffer holds ", partials.numel(),
+                " floats, needs ", sblocks);
+    if (numel == 0) return;
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL(sumsq_partials_kernel, dim3((int)sblocks), dim3(BLOCK),
+                       0, stream, g.data_ptr<float>(),
+                       partials.data_ptr<float>(), step_t.data_ptr<float>(),
+                       numel);
+    long blocks = (numel + BLOCK - 1) / BLOCK;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(flat_adam_partials_kernel, dim3((int)blocks),
+                       dim3(BLOCK), 0, stream, p.data_ptr<float>(),
+                       g.data_ptr<float>(), m.data_ptr<float>(),
+                       v.data_ptr<float>(), step_t.data_ptr<float>(),
+                       partials.data_ptr<float>(), normsq.data_ptr<float>(),
+                       (int)sblocks, numel, (float)clip, (float)lr, (float)b1,
+                       (float)b2, (float)eps);
+}
+
+// number of partials flat_sumsq_adam writes for a buffer of numel floats
+int64_t flat_sumsq_blocks(int64_t numel) {
+    long sblocks = (numel + BLOCK - 1) / BLOCK;
+    return sblocks > SUMSQ_MAX_BLOCKS ? SUMSQ_MAX_BLOCKS : sblocks;
+}

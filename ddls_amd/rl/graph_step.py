@@ -35,6 +35,18 @@ from ..parallel import all_reduce_gradients, is_distributed
 from .rollout import CompactObs
 
 
+def step_fusion_enabled() -> bool:
+    """Mirror of cached_step.hip's launch switch for the optimiser tail:
+    DDLS_AMD_STEP_FUSION=off, or the thread-per-row oracle
+    (DDLS_AMD_ROW_KERNELS=thread), keeps the previous launch sequence."""
+    v = os.environ.get("DDLS_AMD_STEP_FUSION", "")
+    if v not in ("", "on", "off"):
+        raise RuntimeError(
+            f"DDLS_AMD_STEP_FUSION must be 'on' or 'off', got '{v}'")
+    return (v != "off"
+            and os.environ.get("DDLS_AMD_ROW_KERNELS", "") != "thread")
+
+
 class _PPOLossFn(torch.autograd.Function):
     """Fused PPO loss (ops/hip/ppo_loss.hip): one kernel forward, one kernel
     analytic backward — replaces ~100 tiny elementwise kernels per replay."""
@@ -818,11 +830,19 @@ class CapturedSGDStep:
         if self.flat_p is not None:
             # fused grad-clip + Adam over the flat buffers (the norm uses the
             # in-house sumsq kernel: torch reductions drift under replay)
+            hyper = (float(self.cfg.grad_clip or 0.0), float(self.cfg.lr),
+                     0.9, 0.999, 1e-8)
+            if step_fusion_enabled():
+                # two launches: block partials of the norm (+ the step
+                # count), then their fixed-order sum + clip + Adam
+                self._ext.flat_sumsq_adam(
+                    self.flat_p, self.flat_g, self.flat_m, self.flat_v,
+                    self.step_t, self.normsq, self.normsq_partials, *hyper)
+                return
             self._ext.flat_sumsq(self.flat_g, self.normsq)
             self._ext.flat_adam(self.flat_p, self.flat_g, self.flat_m,
                                 self.flat_v, self.step_t, self.normsq,
-                                float(self.cfg.grad_clip or 0.0),
-                                float(self.cfg.lr), 0.9, 0.999, 1e-8)
+                                *hyper)
             return
         if self.cfg.grad_clip is not None:
             torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
@@ -845,6 +865,10 @@ class CapturedSGDStep:
         self.flat_v = torch.zeros(numel, device=dev)
         self.step_t = torch.zeros(1, device=dev)
         self.normsq = torch.zeros(1, device=dev)
+        # block partials of the grad norm (flat_sumsq_adam), next to normsq
+        nparts = (int(self._ext.flat_sumsq_blocks(numel))
+                  if hasattr(self._ext, "flat_sumsq_blocks") else 512)
+        self.normsq_partials = torch.zeros(max(1, nparts), device=dev)
         self._params = params
         self._offs = []
         off = 0
