@@ -29,6 +29,9 @@ _SOURCES = [os.path.join(_HERE, "hip", "meanpool.hip"),
             os.path.join(_HERE, "hip", "cached_step.hip"),
             os.path.join(_HERE, "hip", "batch_stage.hip"),
             os.path.join(_HERE, "hip", "bindings.hip")]
+# headers the sources include: not compiled on their own, but a built library
+# older than one of them is stale
+_HEADERS = [os.path.join(_HERE, "hip", "cs_stage.h")]
 
 
 def build_extensions(verbose: bool = False):
@@ -67,7 +70,8 @@ def _load_prebuilt():
     lib = os.path.join(_BUILD_DIR, name + ".so")
     if os.access(_BUILD_DIR, os.W_OK) or not os.path.isfile(lib):
         return None
-    if any(os.path.getmtime(s) > os.path.getmtime(lib) for s in _SOURCES):
+    if any(os.path.getmtime(s) > os.path.getmtime(lib)
+           for s in _SOURCES + _HEADERS):
         return None
     import importlib.util
     import torch  # noqa: F401  (the library links against torch)

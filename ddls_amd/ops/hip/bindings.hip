@@ -71,6 +71,12 @@ void env_step_batch(std::vector<torch::Tensor> T, std::vector<double> fscal,
                     std::vector<int64_t> iscal);
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs);
 void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs);
+void cached_step_fwd_staged(std::vector<torch::Tensor> T,
+                            std::vector<double> fs,
+                            std::vector<torch::Tensor> store,
+                            torch::Tensor perm, torch::Tensor cursor,
+                            torch::Tensor err,
+                            std::vector<torch::Tensor> dims);
 void cached_stage(std::vector<torch::Tensor> store,
                   std::vector<torch::Tensor> dst, torch::Tensor perm,
                   torch::Tensor cursor, torch::Tensor err,
@@ -124,6 +130,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fully-fused cached-models PPO minibatch forward (GNN+head+loss)");
     m.def("cached_step_bwd", &cached_step_bwd,
           "analytic whole-net backward into the flat grad buffer");
+    m.def("cached_step_fwd_staged", &cached_step_fwd_staged,
+          "cached_step_fwd whose first launch also gathers the minibatch "
+          "from the device batch store (block 0 runs cached_stage's role)");
     m.def("cached_stage", &cached_stage,
           "gather one minibatch from the device batch store into the "
           "cached step's staged inputs; advances the device cursor");

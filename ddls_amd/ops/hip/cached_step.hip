@@ -34,6 +34,14 @@
 //                                    (+ one block for the C_STATS sums)
 //         cs_bwd_w, cs_bwd_w_reduce  all weight grads into flat_g
 //
+// By default two of those carry work that waits for nothing ahead of it in
+// the chain (section "work off the serial chain" below): the first forward
+// launch is cs_fwd_stage_mlp1_lanes (block 0 gathers the minibatch, so the
+// stage kernel's own launch goes away: 15 per replay), and cs_bwd_pool is
+// cs_bwd_pool_wfc, one pool block per model beside the 17 B-row weight-grad
+// blocks that cs_bwd_w then no longer launches.  DDLS_AMD_STEP_OVERLAP=off
+// launches the sequence above.
+//
 // DDLS_AMD_STEP_FUSION=off launches the previous 20 separate kernels and
 // DDLS_AMD_ROW_KERNELS=thread the thread-per-row ones before them; both
 // sets stay in this file unchanged as oracles for bitwise comparison.
@@ -55,6 +63,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+
+// the minibatch stage role (shared with batch_stage.hip)
+#include "cs_stage.h"
 
 #define LN_EPS 1e-5f
 
@@ -2308,6 +2319,440 @@ cs_bwd_scat1_gu1_kernel(CachedPtrs P, CachedDims D) {
 }
 
 // ===========================================================================
+// work off the serial chain (DDLS_AMD_STEP_OVERLAP, default on)
+// ===========================================================================
+//
+// A replay is one serial chain of launches.  Two pieces of work sat on it
+// although nothing ahead of them in the chain produces their inputs; each now
+// rides as extra blocks of a launch that exists anyway (different roles per
+// block index, like the statistics block of cs_bwd_scat1_gu1_kernel), so the
+// chain stays serial and every output element keeps its summation order.
+
+// ---- cs_bwd_pool + the B-row ("special") blocks of cs_bwd_w ----
+// Blocks [0, M): pool role, one block per model.  Block M: the graph-module
+// weight-grad job.  Blocks M+1 .. M+16: the FC-column jobs.  The special jobs
+// read only what cs_head_kernel wrote, so they run here, five launches
+// earlier than in cs_bwd_w_kernel, which is then launched with its row-job
+// blocks only.  Arithmetic is that of cs_bwd_pool_kernel and of
+// cs_bwd_w_kernel's special blocks, term for term; what changes is the
+// staging: a super-tile of up to WFC_ST sample rows per global round trip
+// instead of TILE_K, walked in TILE_K-row tiles so a chain sees the same
+// full / partial tiles as before.
+#define WFC_ST 128        // sample rows per super-tile (a multiple of TILE_K)
+#define WFC_NFC 16        // FC-column blocks
+// LDS floats per role; the kernel's buffer is their maximum (a union)
+#define WFC_LDS_POOL (1024 + WFC_ST * KOUT + KOUT)
+#define WFC_LDS_G (WFC_ST * (KGE + 3 * KGF))
+#define WFC_LDS_FC (WFC_ST * (KFIN + 4 * 16 + KA + 1))
+#define WFC_LDS (WFC_LDS_G > WFC_LDS_FC ? WFC_LDS_G : WFC_LDS_FC)
+static_assert(WFC_LDS >= WFC_LDS_POOL, "pool role LDS");
+static_assert(WFC_LDS * 4 <= 64 * 1024, "cs_bwd_pool_wfc: LDS over 64 KB");
+static_assert(WFC_ST % TILE_K == 0, "super-tile of whole tiles");
+static_assert(KFC / WFC_NFC == 16 && KFC % WFC_NFC == 0, "16 columns a block");
+
+__global__ void __launch_bounds__(256)
+cs_bwd_pool_wfc_kernel(CachedPtrs P, CachedDims D) {
+  __shared__ float lds[WFC_LDS];
+  const int tid = threadIdx.x;
+  constexpr int NT = 256;
+  const int bid = blockIdx.x;
+
+  if (bid < D.M) {
+    // ---- pool role: gpool[m] and this model's gh2 rows ----
+    const int m = bid;
+    int* smid = reinterpret_cast<int*>(lds);            // [1024]
+    float (*sG)[KOUT] = reinterpret_cast<float (*)[KOUT]>(lds + 1024);
+    float* sP = lds + 1024 + WFC_ST * KOUT;             // [KOUT]
+    // read ahead of the chain; used after it
+    const long lo = P.model_nptr[m], hi = P.model_nptr[m + 1];
+    for (int b = tid; b < D.B; b += NT) smid[b] = (int)P.model_ids[b];
+    float acc = 0.f;
+    for (int t0 = 0; t0 < D.B; t0 += WFC_ST) {
+      const int bt = min(WFC_ST, D.B - t0);
+      float rG[WFC_ST * KOUT / NT];
+#pragma unroll
+      for (int k = 0; k < WFC_ST * KOUT / NT; ++k) {
+        const int x = min(tid + k * NT, bt * KOUT - 1);
+        rG[k] = P.gfinal[(long)(t0 + x / KOUT) * KFIN + x % KOUT];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < WFC_ST * KOUT / NT; ++k) {
+        const int x = tid + k * NT;
+        if (x < bt * KOUT) sG[x / KOUT][x % KOUT] = rG[k];
+      }
+      __syncthreads();
+      if (tid < KOUT) {
+        if (bt == WFC_ST) {
+#pragma unroll 8
+          for (int b = 0; b < WFC_ST; ++b)
+            acc += (smid[t0 + b] == m) ? sG[b][tid] : 0.f;
+        } else {
+          for (int b = 0; b < bt; ++b)
+            acc += (smid[t0 + b] == m) ? sG[b][tid] : 0.f;
+        }
+      }
+    }
+    if (tid < KOUT) {
+      P.gpool[(long)m * KOUT + tid] = acc;
+      sP[tid] = acc;
+    }
+    __syncthreads();
+    const float nn = (float)(hi - lo);
+    for (long u = lo * KOUT + tid; u < hi * KOUT; u += NT)
+      P.gh2[u] = sP[u % KOUT] / nn;
+    return;
+  }
+
+  if (bid == D.M) {
+    // ---- graph module: Wg[GEMB,GFin], bg; LN gamma/beta from gu34 + xh34.
+    // gpre rows are gfinal[:, KOUT:KOUT+KGE] (row stride KFIN).
+    float (*tG)[KGE] = reinterpret_cast<float (*)[KGE]>(lds);
+    float (*tU)[KGF] = reinterpret_cast<float (*)[KGF]>(lds + WFC_ST * KGE);
+    float (*tXH)[KGF] =
+        reinterpret_cast<float (*)[KGF]>(lds + WFC_ST * (KGE + KGF));
+    float (*tGU)[KGF] =
+        reinterpret_cast<float (*)[KGF]>(lds + WFC_ST * (KGE + 2 * KGF));
+    const float* __restrict__ gam = WP(W_LN_G_W);
+    const float* __restrict__ bet = WP(W_LN_G_B);
+    constexpr int UNITS = KGE * KGF;
+    constexpr int MYU = (UNITS + 255) / 256;
+    float acc[MYU];
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) acc[q] = 0.f;
+    // tid in [64, 64+KGE): bias sums; tid in [128, 128+KGF): LN gamma/beta
+    float bacc = 0.f, lacc_w = 0.f, lacc_b = 0.f;
+    for (int r0 = 0; r0 < D.B; r0 += WFC_ST) {
+      const int rt = min(WFC_ST, D.B - r0);
+      // Every global load of the super-tile is issued before the first LDS
+      // store: constant trip counts, indices clamped instead of branched on
+      // so the loads share a basic block.  One round trip per super-tile.
+      {
+        constexpr int CG = WFC_ST * KGE / NT, CX = WFC_ST * KGF / NT;
+        static_assert(CG * NT == WFC_ST * KGE && CX * NT == WFC_ST * KGF,
+                      "whole trips");
+        float rG[CG], rXH[CX], rGU[CX], rGam[CX], rBet[CX];
+#pragma unroll
+        for (int k = 0; k < CG; ++k) {
+          const int x = min(tid + k * NT, rt * KGE - 1);
+          rG[k] = P.gfinal[(long)(r0 + x / KGE) * KFIN + KOUT + x % KGE];
+        }
+#pragma unroll
+        for (int k = 0; k < CX; ++k) {
+          const int x = min(tid + k * NT, rt * KGF - 1);
+          rXH[k] = P.xh34[(long)r0 * KGF + x];
+          rGU[k] = P.gu34[(long)r0 * KGF + x];
+          rGam[k] = gam[x % KGF];
+          rBet[k] = bet[x % KGF];
+        }
+#pragma unroll
+        for (int k = 0; k < CG; ++k) {
+          const int x = tid + k * NT;
+          if (x < rt * KGE) tG[x / KGE][x % KGE] = rG[k];
+        }
+#pragma unroll
+        for (int k = 0; k < CX; ++k) {
+          const int x = tid + k * NT;
+          if (x < rt * KGF) {
+            const int t = x / KGF, i = x % KGF;
+            tU[t][i] = FMA(rXH[k], rGam[k], rBet[k]);
+            tXH[t][i] = rXH[k];
+            tGU[t][i] = rGU[k];
+          }
+        }
+      }
+      __syncthreads();
+      // a full super-tile has constant trip counts: the LDS reads of a chain
+      // run ahead of its adds
+#pragma unroll
+      for (int q = 0; q < MYU; ++q) {
+        int u = tid + q * 256;
+        if (u < UNITS) {
+          int o = u / KGF, i = u % KGF;
+          float a = acc[q];
+          if (rt == WFC_ST) {
+#pragma unroll 16
+            for (int t = 0; t < WFC_ST; ++t) a = FMA(tG[t][o], tU[t][i], a);
+          } else {
+            for (int t = 0; t < rt; ++t) a = FMA(tG[t][o], tU[t][i], a);
+          }
+          acc[q] = a;
+        }
+      }
+      if (tid >= 64 && tid < 64 + KGE) {
+        if (rt == WFC_ST) {
+#pragma unroll 16
+          for (int t = 0; t < WFC_ST; ++t) bacc = bacc + tG[t][tid - 64];
+        } else {
+          for (int t = 0; t < rt; ++t) bacc = bacc + tG[t][tid - 64];
+        }
+      }
+      if (tid >= 128 && tid < 128 + KGF) {
+        if (rt == WFC_ST) {
+#pragma unroll 16
+          for (int t = 0; t < WFC_ST; ++t) {
+            lacc_w = lacc_w + mul_rn(tGU[t][tid - 128], tXH[t][tid - 128]);
+            lacc_b = lacc_b + tGU[t][tid - 128];
+          }
+        } else {
+          for (int t = 0; t < rt; ++t) {
+            lacc_w = lacc_w + mul_rn(tGU[t][tid - 128], tXH[t][tid - 128]);
+            lacc_b = lacc_b + tGU[t][tid - 128];
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) {
+      int u = tid + q * 256;
+      if (u < UNITS) WG_(W_G_W)[u] = acc[q];
+    }
+    if (tid >= 64 && tid < 64 + KGE) WG_(W_G_B)[tid - 64] = bacc;
+    if (tid >= 128 && tid < 128 + KGF) {
+      WG_(W_LN_G_W)[tid - 128] = lacc_w;
+      WG_(W_LN_G_B)[tid - 128] = lacc_b;
+    }
+    return;
+  }
+
+  // ---- FC-column jobs: block jb owns columns [j0, j0 + 16) of W1p/W1v
+  // [FC,FIN] (+ b1p/b1v) AND of W2p [A,FC] / W2v [FC]; block 0 also sums b2p
+  // and b2v.
+  {
+    constexpr int JW = KFC / WFC_NFC;   // 16
+    const int jb = bid - D.M - 1;
+    if (jb >= WFC_NFC) return;
+    const int j0 = jb * JW;
+    float* q_ = lds;
+    float (*tF)[KFIN] = reinterpret_cast<float (*)[KFIN]>(q_);
+    q_ += WFC_ST * KFIN;
+    float (*tGp)[16] = reinterpret_cast<float (*)[16]>(q_);
+    q_ += WFC_ST * 16;
+    float (*tGv)[16] = reinterpret_cast<float (*)[16]>(q_);
+    q_ += WFC_ST * 16;
+    float (*tHp)[16] = reinterpret_cast<float (*)[16]>(q_);
+    q_ += WFC_ST * 16;
+    float (*tHv)[16] = reinterpret_cast<float (*)[16]>(q_);
+    q_ += WFC_ST * 16;
+    float (*tGL)[KA] = reinterpret_cast<float (*)[KA]>(q_);
+    q_ += WFC_ST * KA;
+    float* tGV = q_;                                    // [WFC_ST]
+    constexpr int MYU = (16 * KFIN + 255) / 256;
+    constexpr int MYU2 = (16 * KA + 255) / 256;
+    float accp[MYU], accv[MYU], acc2[MYU2];
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) { accp[q] = 0.f; accv[q] = 0.f; }
+#pragma unroll
+    for (int q = 0; q < MYU2; ++q) acc2[q] = 0.f;
+    // The single-chain sums sit in the waves with the fewest weight units
+    // (units fill tid 0.. upwards).  tid in [192, 192+JW): column sums
+    // b1p/b1v and the W2v column; jb == 0 only: tid in [128, 128+KA) sums
+    // b2p, tid == 128+KA sums b2v
+    const int cj = tid - 192;
+    float bp = 0.f, bv = 0.f, w2v = 0.f, b2 = 0.f;
+    for (int s0 = 0; s0 < D.B; s0 += WFC_ST) {
+      const int st = min(WFC_ST, D.B - s0);
+      // as in the graph-module role: all global loads of the super-tile
+      // first (clamped indices, one basic block), then the LDS stores
+      {
+        constexpr int CF = WFC_ST * KFIN / NT, CJ = WFC_ST * JW / NT;
+        constexpr int CL = (WFC_ST * KA + NT - 1) / NT;
+        static_assert(CF * NT == WFC_ST * KFIN && CJ * NT == WFC_ST * JW
+                      && WFC_ST <= NT, "whole trips");
+        float rF[CF], rGp[CJ], rGv[CJ], rHp[CJ], rHv[CJ], rGL[CL];
+#pragma unroll
+        for (int k = 0; k < CF; ++k) {
+          const int x = min(tid + k * NT, st * KFIN - 1);
+          rF[k] = P.fin[(long)s0 * KFIN + x];
+        }
+#pragma unroll
+        for (int k = 0; k < CJ; ++k) {
+          const int x = min(tid + k * NT, st * JW - 1);
+          const long g = (long)(s0 + x / JW) * KFC + j0 + x % JW;
+          rGp[k] = P.gh1p[g];
+          rGv[k] = P.gh1v[g];
+          rHp[k] = P.h1p[g];
+          rHv[k] = P.h1v[g];
+        }
+#pragma unroll
+        for (int k = 0; k < CL; ++k) {
+          const int x = min(tid + k * NT, st * KA - 1);
+          rGL[k] = P.glogits[(long)s0 * KA + x];
+        }
+        const float rGV = P.gvalue[s0 + min(tid, st - 1)];
+#pragma unroll
+        for (int k = 0; k < CF; ++k) {
+          const int x = tid + k * NT;
+          if (x < st * KFIN) tF[x / KFIN][x % KFIN] = rF[k];
+        }
+#pragma unroll
+        for (int k = 0; k < CJ; ++k) {
+          const int x = tid + k * NT;
+          if (x < st * JW) {
+            const int t = x / JW, j = x % JW;
+            tGp[t][j] = rGp[k];
+            tGv[t][j] = rGv[k];
+            tHp[t][j] = rHp[k];
+            tHv[t][j] = rHv[k];
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < CL; ++k) {
+          const int x = tid + k * NT;
+          if (x < st * KA) tGL[x / KA][x % KA] = rGL[k];
+        }
+        if (tid < st) tGV[tid] = rGV;
+      }
+      __syncthreads();
+      // the super-tile in TILE_K-row tiles: each chain sees the full and
+      // partial tiles cs_bwd_w_kernel's special blocks saw
+      for (int r0 = 0; r0 < st; r0 += TILE_K) {
+        const int rt = min(TILE_K, st - r0);
+#pragma unroll
+        for (int q = 0; q < MYU; ++q) {
+          int u = tid + q * NT;
+          if (u < JW * KFIN) {
+            int j = u / KFIN, i = u % KFIN;
+            float ap = accp[q], av = accv[q];
+            if (rt == TILE_K) {
+#pragma unroll
+              for (int t = 0; t < TILE_K; ++t) {
+                ap = FMA(tGp[r0 + t][j], tF[r0 + t][i], ap);
+                av = FMA(tGv[r0 + t][j], tF[r0 + t][i], av);
+              }
+            } else {
+              for (int t = 0; t < rt; ++t) {
+                ap = FMA(tGp[r0 + t][j], tF[r0 + t][i], ap);
+                av = FMA(tGv[r0 + t][j], tF[r0 + t][i], av);
+              }
+            }
+            accp[q] = ap;
+            accv[q] = av;
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < MYU2; ++q) {
+          int u = tid + q * NT;
+          if (u < KA * JW) {
+            int a = u / JW, j = u % JW;
+            float s = acc2[q];
+            if (rt == TILE_K) {
+#pragma unroll
+              for (int t = 0; t < TILE_K; ++t) {
+                // a full tile's first 20 terms are fused, the last 12 are
+                // rounded products; a partial tile is fused throughout
+                if (t < 20) s = FMA(tGL[r0 + t][a], tHp[r0 + t][j], s);
+                else s = s + mul_rn(tGL[r0 + t][a], tHp[r0 + t][j]);
+              }
+            } else {
+              for (int t = 0; t < rt; ++t)
+                s = FMA(tGL[r0 + t][a], tHp[r0 + t][j], s);
+            }
+            acc2[q] = s;
+          }
+        }
+      }
+      if (cj >= 0 && cj < JW) {
+        if (st == WFC_ST) {
+#pragma unroll 16
+          for (int t = 0; t < WFC_ST; ++t) {
+            bp = bp + tGp[t][cj];
+            bv = bv + tGv[t][cj];
+            w2v = FMA(tGV[t], tHv[t][cj], w2v);
+          }
+        } else {
+          for (int t = 0; t < st; ++t) {
+            bp = bp + tGp[t][cj];
+            bv = bv + tGv[t][cj];
+            w2v = FMA(tGV[t], tHv[t][cj], w2v);
+          }
+        }
+      }
+      if (jb == 0) {
+        if (tid >= 128 && tid < 128 + KA) {
+          if (st == WFC_ST) {
+#pragma unroll 16
+            for (int t = 0; t < WFC_ST; ++t) b2 = b2 + tGL[t][tid - 128];
+          } else {
+            for (int t = 0; t < st; ++t) b2 = b2 + tGL[t][tid - 128];
+          }
+        }
+        if (tid == 128 + KA) {
+          if (st == WFC_ST) {
+#pragma unroll 16
+            for (int t = 0; t < WFC_ST; ++t) b2 = b2 + tGV[t];
+          } else {
+            for (int t = 0; t < st; ++t) b2 = b2 + tGV[t];
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) {
+      int u = tid + q * NT;
+      if (u < JW * KFIN) {
+        int j = u / KFIN, i = u % KFIN;
+        WG_(W_P1_W)[(long)(j0 + j) * KFIN + i] = accp[q];
+        WG_(W_V1_W)[(long)(j0 + j) * KFIN + i] = accv[q];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < MYU2; ++q) {
+      int u = tid + q * NT;
+      if (u < KA * JW) {
+        int a = u / JW, j = u % JW;
+        WG_(W_P2_W)[(long)a * KFC + j0 + j] = acc2[q];
+      }
+    }
+    if (cj >= 0 && cj < JW) {
+      WG_(W_P1_B)[j0 + cj] = bp;
+      WG_(W_V1_B)[j0 + cj] = bv;
+      WG_(W_V2_W)[j0 + cj] = w2v;
+    }
+    if (jb == 0) {
+      if (tid >= 128 && tid < 128 + KA) WG_(W_P2_B)[tid - 128] = b2;
+      if (tid == 128 + KA) WG_(W_V2_B)[0] = b2;
+    }
+  }
+}
+
+// ---- cs_stage + cs_fwd_mlp_lanes<1> ----
+// Block 0 gathers the minibatch from the device batch store (the body of
+// cs_stage_kernel, one workgroup, same cursor protocol and guards); blocks
+// 1.. are cs_fwd_mlp_lanes_kernel<1, L>'s blocks 0.. .  No GNN forward kernel
+// reads a staged buffer (cs_head_kernel is their first reader), so the two
+// roles are independent and one launch of the chain goes away.
+static_assert(CS_STAGE_THREADS == ROW_NT, "stage role runs a ROW_NT block");
+
+template <int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_fwd_stage_mlp1_lanes_kernel(CachedPtrs P, CachedDims D, StagePtrs SP,
+                               StageDims SD) {
+  if (blockIdx.x == 0) {
+    cs_stage_body(SP, SD);
+    return;
+  }
+  constexpr int RPB = ROW_NT / L;
+  const int blk = (int)blockIdx.x - 1;
+  const int nbN = (D.N + RPB - 1) / RPB;
+  if (blk < nbN) {
+    const long r0 = (long)blk * RPB;
+    rows_fwd_lanes<KF0, KH, 1, L>(
+        P, W_LN_N1_W, r0, D.N,
+        [&](long v, int i) { return P.z0[v * KF0 + i]; },
+        P.xh_z1, P.rst_z1, P.hn1);
+  } else {
+    const long r0 = (long)(blk - nbN) * RPB;
+    rows_fwd_lanes<KFE, KH, 0, L>(
+        P, W_LN_E1_W, r0, D.E,
+        [&](long k, int i) { return P.e[k * KFE + i]; },
+        P.xh_e1, P.rst_e1, P.he1);
+  }
+}
+
+// ===========================================================================
 // host bindings
 // ===========================================================================
 
@@ -2321,10 +2766,16 @@ cs_bwd_scat1_gu1_kernel(CachedPtrs P, CachedDims D) {
 //                                two 32x64 reduce-module-1 kernels, else 16.
 //   DDLS_AMD_STEP_FUSION=off     the separate kernels of every fused launch
 //                                (oracle / A/B); 'thread' above implies it
+//   DDLS_AMD_STEP_OVERLAP=off    cs_stage, cs_bwd_pool and the B-row blocks
+//                                of cs_bwd_w as launches / blocks of their
+//                                own (oracle / A/B); STEP_FUSION=off and
+//                                'thread' imply it
 struct RowCfg {
   bool thread;
   int lanes;   // 0: per-kernel default
   bool fused;  // the fused launches (needs the lane-parallel row kernels)
+  bool overlap;  // independent work rides in launches that exist anyway
+                 // (needs the fused launches)
 };
 
 static RowCfg row_cfg() {
@@ -2349,6 +2800,12 @@ static RowCfg row_cfg() {
               "cached_step: DDLS_AMD_STEP_FUSION must be 'on' or 'off', got '",
               sf, "'");
   c.fused = !off && !c.thread;
+  const char* so = getenv("DDLS_AMD_STEP_OVERLAP");
+  const bool ooff = (so != nullptr && strcmp(so, "off") == 0);
+  TORCH_CHECK(so == nullptr || so[0] == '\0' || ooff || strcmp(so, "on") == 0,
+              "cached_step: DDLS_AMD_STEP_OVERLAP must be 'on' or 'off', got '",
+              so, "'");
+  c.overlap = !ooff && c.fused;
   return c;
 }
 
@@ -2506,11 +2963,11 @@ static void fill_ptrs(CachedPtrs& P, CachedDims& D, RowCfg& R,
               "cached_step: wg_scratch too small");
 }
 
-void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
-  CachedPtrs P;
-  CachedDims D;
-  RowCfg R;
-  fill_ptrs(P, D, R, T, fs);
+// the forward launches; with SP/SD (cached_step_fwd_staged, overlap mode) the
+// first one carries the stage role in its block 0
+static void step_fwd_launches(const CachedPtrs& P, const CachedDims& D,
+                              const RowCfg& R, const StagePtrs* SP,
+                              const StageDims* SD) {
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   const int rows_b = (D.N + D.E + 255) / 256;
   const int comb1_b = ((long)D.N * D.HID + 255) / 256;
@@ -2521,7 +2978,22 @@ void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
     hipLaunchKernelGGL(cs_fwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
   } else {
-    LAUNCH_ROWS(K_FWD_MLP1, 16, D.N, D.E);
+    if (SP != nullptr) {
+      const int L_ = R.lanes ? R.lanes : 16;
+      const int rpb_ = ROW_NT / L_;
+      const dim3 grid(1 + (D.N + rpb_ - 1) / rpb_ + (D.E + rpb_ - 1) / rpb_);
+      if (L_ == 8)
+        hipLaunchKernelGGL(cs_fwd_stage_mlp1_lanes_kernel<8>, grid,
+                           dim3(ROW_NT), 0, stream, P, D, *SP, *SD);
+      else if (L_ == 16)
+        hipLaunchKernelGGL(cs_fwd_stage_mlp1_lanes_kernel<16>, grid,
+                           dim3(ROW_NT), 0, stream, P, D, *SP, *SD);
+      else
+        hipLaunchKernelGGL(cs_fwd_stage_mlp1_lanes_kernel<32>, grid,
+                           dim3(ROW_NT), 0, stream, P, D, *SP, *SD);
+    } else {
+      LAUNCH_ROWS(K_FWD_MLP1, 16, D.N, D.E);
+    }
     LAUNCH_ROWS(K_FWD_RED1, 32, D.E, D.N);
   }
   if (!R.fused)
@@ -2566,6 +3038,39 @@ void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
                      0, stream, P, D);
 }
 
+void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
+  CachedPtrs P;
+  CachedDims D;
+  RowCfg R;
+  fill_ptrs(P, D, R, T, fs);
+  step_fwd_launches(P, D, R, nullptr, nullptr);
+}
+
+// cached_step_fwd with the minibatch gathered from the device batch store by
+// block 0 of the first launch (overlap mode only: the caller launches
+// cached_stage itself otherwise).  store / perm / cursor / err / dims are
+// cached_stage's arguments; the destinations are T's own staged inputs.
+void cached_step_fwd_staged(std::vector<torch::Tensor> T,
+                            std::vector<double> fs,
+                            std::vector<torch::Tensor> store,
+                            torch::Tensor perm, torch::Tensor cursor,
+                            torch::Tensor err,
+                            std::vector<torch::Tensor> dims) {
+  CachedPtrs P;
+  CachedDims D;
+  RowCfg R;
+  fill_ptrs(P, D, R, T, fs);
+  TORCH_CHECK(R.overlap, "cached_step_fwd_staged: needs the lane-parallel "
+              "fused launches with DDLS_AMD_STEP_OVERLAP on");
+  StagePtrs SP;
+  StageDims SD;
+  cs_stage_args(SP, SD, "cached_step_fwd_staged", store,
+                {T[C_GF], T[C_MASK], T[C_MODEL_IDS], T[C_ACTIONS],
+                 T[C_OLD_LOGP], T[C_ADV], T[C_VTARG]},
+                perm, cursor, err, dims);
+  step_fwd_launches(P, D, R, &SP, &SD);
+}
+
 void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
   CachedPtrs P;
   CachedDims D;
@@ -2581,8 +3086,14 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
   if (!R.fused)
     hipLaunchKernelGGL(cs_bwd_head_kernel, dim3(hb), dim3(256), 0, stream,
                        P, D);
-  hipLaunchKernelGGL(cs_bwd_pool_kernel, dim3(1), dim3(512), 0, stream,
-                     P, D);
+  if (R.overlap)
+    // one pool block per model + the graph-module block + the FC-column
+    // blocks, which cs_bwd_w below then does not launch
+    hipLaunchKernelGGL(cs_bwd_pool_wfc_kernel, dim3(D.M + 1 + WFC_NFC),
+                       dim3(256), 0, stream, P, D);
+  else
+    hipLaunchKernelGGL(cs_bwd_pool_kernel, dim3(1), dim3(512), 0, stream,
+                       P, D);
   if (R.thread)
     hipLaunchKernelGGL(cs_bwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
@@ -2627,8 +3138,11 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
                          0, stream, P, D);
   }
   const int nsplit = D.wgrad_mfma ? 1 : WSPLIT;
-  // 6 row jobs x nsplit, the graph-module block, 16 FC-column blocks
-  hipLaunchKernelGGL(cs_bwd_w_kernel, dim3(6 * nsplit + 1 + 16), dim3(256),
+  // 6 row jobs x nsplit, the graph-module block, 16 FC-column blocks; in
+  // overlap mode the 17 B-row blocks ran in cs_bwd_pool_wfc above, and with
+  // the row-job grid their paths are never entered
+  hipLaunchKernelGGL(cs_bwd_w_kernel,
+                     dim3(6 * nsplit + (R.overlap ? 0 : 1 + 16)), dim3(256),
                      0, stream, P, D);
   if (nsplit > 1)
     hipLaunchKernelGGL(cs_bwd_w_reduce_kernel, dim3(6), dim3(256), 0,

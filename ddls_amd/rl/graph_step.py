@@ -47,6 +47,17 @@ def step_fusion_enabled() -> bool:
             and os.environ.get("DDLS_AMD_ROW_KERNELS", "") != "thread")
 
 
+def step_overlap_enabled() -> bool:
+    """Mirror of cached_step.hip's DDLS_AMD_STEP_OVERLAP switch (default on):
+    the stage role rides in the step's first forward launch.  It needs the
+    fused launches, so whatever turns those off turns this off too."""
+    v = os.environ.get("DDLS_AMD_STEP_OVERLAP", "")
+    if v not in ("", "on", "off"):
+        raise RuntimeError(
+            f"DDLS_AMD_STEP_OVERLAP must be 'on' or 'off', got '{v}'")
+    return v != "off" and step_fusion_enabled()
+
+
 class _PPOLossFn(torch.autograd.Function):
     """Fused PPO loss (ops/hip/ppo_loss.hip): one kernel forward, one kernel
     analytic backward — replaces ~100 tiny elementwise kernels per replay."""
@@ -211,8 +222,18 @@ class _FusedCachedEngine:
                       float(c.vf_loss_coeff), float(c.entropy_coeff)]
         self.ext = ext
 
-    def run(self):
-        self.ext.cached_step_fwd(self.scratch, self.fscal)
+    def run(self, store=None):
+        """One fwd+bwd.  With a ``DeviceBatchStore`` the minibatch is gathered
+        from it first: inside the first forward launch when the overlap
+        switch is on, by the stage kernel's own launch otherwise."""
+        if store is not None and step_overlap_enabled():
+            self.ext.cached_step_fwd_staged(
+                self.scratch, self.fscal, store.tensors(), store.perm,
+                store.cursor, store.err, [store.n_rows, store.n_mb])
+        else:
+            if store is not None:
+                store.stage_into(self.ext, self.st.d)
+            self.ext.cached_step_fwd(self.scratch, self.fscal)
         self.ext.cached_step_bwd(self.scratch, self.fscal)
 
 
@@ -732,16 +753,19 @@ class CapturedSGDStep:
 
     def _body_fwd_bwd(self):
         cfg, B = self.cfg, self.B
+        if self._fused_cached is not None:
+            # fully-fused path, grads straight into flat_g.  With a device
+            # batch store the gather of this minibatch's rows rides in the
+            # first forward launch (DDLS_AMD_STEP_OVERLAP=off: the stage
+            # kernel's own launch in front, as below)
+            self._fused_cached.run(self.store)
+            return
         if self.store is not None:
             # first node of the chain: gather this minibatch's rows from the
             # device batch store into the d-buffers everything below reads
             from .. import ops as hip_ops
             self.store.stage_into(hip_ops.get_extension(required=True),
                                   self.d)
-        if self._fused_cached is not None:
-            # fully-fused path: two kernels, grads straight into flat_g
-            self._fused_cached.run()
-            return
         if self.flat_p is None:
             # flat engine zeroes grads inside flat_adam instead
             grads = [pa.grad for pa in self.policy.parameters()
