@@ -46,6 +46,12 @@ void flat_sumsq_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                      torch::Tensor normsq, torch::Tensor partials,
                      double clip, double lr, double b1, double b2,
                      double eps);
+void flat_sumsq_adam_folded(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                            torch::Tensor v, torch::Tensor step_t,
+                            torch::Tensor normsq, torch::Tensor partials,
+                            torch::Tensor scratch, std::vector<int64_t> segs,
+                            int64_t nsplit, int64_t stride, double clip,
+                            double lr, double b1, double b2, double eps);
 int64_t flat_sumsq_blocks(int64_t numel);
 std::vector<torch::Tensor> head_fwd(
     torch::Tensor gm, torch::Tensor gf, torch::Tensor mask,
@@ -70,7 +76,10 @@ std::vector<torch::Tensor> ppo_loss_bwd(
 void env_step_batch(std::vector<torch::Tensor> T, std::vector<double> fscal,
                     std::vector<int64_t> iscal);
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs);
-void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs);
+void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs,
+                     bool defer_reduce);
+bool cached_step_reduce_deferred(bool defer_reduce);
+std::vector<int64_t> cached_step_fold_segments(std::vector<int64_t> offs);
 void cached_step_fwd_staged(std::vector<torch::Tensor> T,
                             std::vector<double> fs,
                             std::vector<torch::Tensor> store,
@@ -129,7 +138,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cached_step_fwd", &cached_step_fwd,
           "fully-fused cached-models PPO minibatch forward (GNN+head+loss)");
     m.def("cached_step_bwd", &cached_step_bwd,
-          "analytic whole-net backward into the flat grad buffer");
+          "analytic whole-net backward into the flat grad buffer; with "
+          "defer_reduce the row jobs' partial sums stay in wg_scratch for "
+          "flat_sumsq_adam_folded",
+          pybind11::arg("T"), pybind11::arg("fs"),
+          pybind11::arg("defer_reduce") = false);
+    m.def("cached_step_reduce_deferred", &cached_step_reduce_deferred,
+          "whether cached_step_bwd(defer_reduce) leaves the reduce to the "
+          "tail under the current switches");
+    m.def("cached_step_fold_segments", &cached_step_fold_segments,
+          "the row jobs' (flat start, length, scratch offset) triples, then "
+          "the split count and the split stride, from the host slot offsets");
+    m.def("flat_sumsq_adam_folded", &flat_sumsq_adam_folded,
+          "flat_sumsq_adam whose first launch also sums the row-split "
+          "weight-grad partials into the flat gradient");
     m.def("cached_step_fwd_staged", &cached_step_fwd_staged,
           "cached_step_fwd whose first launch also gathers the minibatch "
           "from the device batch store (block 0 runs cached_stage's role)");

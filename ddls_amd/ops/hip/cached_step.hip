@@ -42,6 +42,13 @@
 // blocks that cs_bwd_w then no longer launches.  DDLS_AMD_STEP_OVERLAP=off
 // launches the sequence above.
 //
+// By default three pairs of those are merged along row-local dependencies
+// (DDLS_AMD_STEP_MERGE, sections "cs_stage + round-1 node / edge modules +
+// round-1 reduce module" and "cs_bwd_scat1_gu1 + the row jobs of cs_bwd_w"
+// below): the first two forward launches are one, cs_bwd_scat1_gu1 and
+// cs_bwd_w are one, and cs_bwd_w_reduce's sums are formed by the first
+// kernel of the optimiser tail when the caller defers them: 12 per replay.
+//
 // DDLS_AMD_STEP_FUSION=off launches the previous 20 separate kernels and
 // DDLS_AMD_ROW_KERNELS=thread the thread-per-row ones before them; both
 // sets stay in this file unchanged as oracles for bitwise comparison.
@@ -2752,6 +2759,551 @@ cs_fwd_stage_mlp1_lanes_kernel(CachedPtrs P, CachedDims D, StagePtrs SP,
   }
 }
 
+// ---- cs_stage + round-1 node / edge modules + round-1 reduce module ----
+// The round-1 modules are 5 -> 16 and 2 -> 16: a reduce-module block can
+// compute hn1[src[k]] and he1[k] for its own message rows from z0 / e while
+// it stages them, which is cheaper than a launch of its own and a
+// src -> hn1 gather through memory.  Block 0 (with a device batch store) is
+// the stage role; then cs_fwd_reduce_lanes_kernel<1, L>'s edge-row and
+// self-row blocks.  Every tensor the two launches stored is still stored,
+// once: he1 / xh_e1 / rst_e1 by the edge block that owns the edge, hn1 /
+// xh_z1 / rst_z1 by the self-row block that owns the node (an edge block
+// recomputes hn1[src] and does not store it).  DDLS_AMD_STEP_MERGE=off
+// launches the two kernels above.
+
+// one output element of a round-1 module row: rows_fwd_lanes<Din, KH, NF, .>'s
+// operation sequence on the Din inputs at x; *xh_c is xhat[c]
+template <int Din, int NF>
+__device__ __forceinline__ float mod1_elem(
+    const float* __restrict__ x, const float* __restrict__ gam,
+    const float* __restrict__ bet, const float* __restrict__ w, float b,
+    int c, float* __restrict__ xh_c, float* __restrict__ rstd_out) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < Din; ++i) s = s + x[i];
+  const float mu = s / Din;
+  float var;
+  {
+    const float d0 = x[0] - mu;
+    var = d0 * d0;
+  }
+#pragma unroll
+  for (int i = 1; i < Din; ++i) {
+    const float d = x[i] - mu;
+    if (i >= Din - NF) var = FMA(d, d, var);
+    else var = var + d * d;
+  }
+  float rstd;
+  if ((Din & (Din - 1)) == 0) rstd = rsqrtf(FMA(var, 1.f / Din, LN_EPS));
+  else rstd = rsqrtf(var / Din + LN_EPS);
+  *rstd_out = rstd;
+  *xh_c = (x[c] - mu) * rstd;
+  float acc = b;
+#pragma unroll
+  for (int i = 0; i < Din; ++i) {
+    const float xh = (x[i] - mu) * rstd;
+    acc = FMA(FMA(xh, gam[i], bet[i]), w[i], acc);
+  }
+  return acc > 0.f ? acc : 0.f;
+}
+
+template <int L, bool EDGE>
+__device__ __forceinline__ void mlp1_red1_rows(const CachedPtrs& P, long r0,
+                                               long nrows) {
+  constexpr int RPB = ROW_NT / L;
+  constexpr int XS = KMSG + 1;
+  constexpr int RW = EDGE ? KF0 + KFE : KF0;     // staged inputs per row
+  constexpr int NSM = 2 * KMSG + KHID + (2 * KF0 + KH * KF0 + KH)
+                      + (EDGE ? 2 * KFE + KH * KFE + KH : 0);
+  constexpr int WQ = KMSG * KHID / ROW_NT;
+  static_assert(RPB * RW <= ROW_NT && NSM <= 2 * ROW_NT
+                && KMSG * KHID % ROW_NT == 0, "one staging pass");
+  __shared__ float sGam[KMSG], sBet[KMSG], sW[KHID * XS], sB[KHID];
+  __shared__ float sX[RPB * XS], sU[RPB * XS];
+  // gam | bet | W | b of the node module, then of the edge module
+  __shared__ float sM1[2 * KF0 + KH * KF0 + KH + 2 * KFE + KH * KFE + KH];
+  __shared__ float sIn[RPB * (KF0 + KFE)];
+  float* const sGamN = sM1;
+  float* const sBetN = sGamN + KF0;
+  float* const sWN = sBetN + KF0;
+  float* const sBN = sWN + KH * KF0;
+  float* const sGamE = sBN + KH;
+  float* const sBetE = sGamE + KFE;
+  float* const sWE = sBetE + KFE;
+  float* const sBE = sWE + KH * KFE;
+  const int tid = threadIdx.x;
+  // the small parameter vectors as one index space: global source and LDS
+  // destination of element x
+  auto small = [&](int x, const float*& src, float*& dst) {
+    const int seg[12] = {KMSG, KMSG, KHID, KF0, KF0, KH * KF0, KH,
+                         KFE, KFE, KH * KFE, KH, 0};
+    const int slot[11] = {W_LN_R1_W, W_LN_R1_B, W_R1_B,
+                          W_LN_N1_W, W_LN_N1_B, W_N1_W, W_N1_B,
+                          W_LN_E1_W, W_LN_E1_B, W_E1_W, W_E1_B};
+    float* const lds[11] = {sGam, sBet, sB, sGamN, sBetN, sWN, sBN,
+                            sGamE, sBetE, sWE, sBE};
+    src = nullptr;
+    dst = nullptr;
+#pragma unroll
+    for (int q = 0; q < 11; ++q) {
+      if (x >= 0 && x < seg[q]) {
+        src = WP(slot[q]) + x;
+        dst = lds[q] + x;
+      }
+      x -= seg[q];
+    }
+  };
+  // every global load of the thread before its first LDS store
+  float wr[WQ];
+  {
+    const float* __restrict__ gW = WP(W_R1_W);
+#pragma unroll
+    for (int q = 0; q < WQ; ++q) wr[q] = gW[tid + q * ROW_NT];
+  }
+  const float* sm_src[2];
+  float* sm_dst[2];
+  float sm_val[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int x = tid + q * ROW_NT;
+    small(x < NSM ? x : -1, sm_src[q], sm_dst[q]);
+    sm_val[q] = sm_src[q] != nullptr ? *sm_src[q] : 0.f;
+  }
+  float in_val = 0.f;
+  if (tid < RPB * RW) {
+    const int r = tid / RW, c = tid % RW;
+    const long row = r0 + r;
+    if (row < nrows) {
+      if (EDGE)
+        in_val = c < KF0 ? P.z0[P.src[row] * KF0 + c]
+                         : P.e[row * KFE + (c - KF0)];
+      else
+        in_val = P.z0[row * KF0 + c];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < WQ; ++q) {
+    const int x = tid + q * ROW_NT;
+    sW[(x / KMSG) * XS + x % KMSG] = wr[q];
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    if (sm_dst[q] != nullptr) *sm_dst[q] = sm_val[q];
+  if (tid < RPB * RW)
+    sIn[(tid / RW) * (KF0 + KFE) + tid % RW] = in_val;
+  __syncthreads();
+  // the message rows: one thread per element, node-module elements first so
+  // that a wave runs one module
+  constexpr int NEL = RPB * KH;
+  for (int x = tid; x < (EDGE ? 2 : 1) * NEL; x += ROW_NT) {
+    const bool node = x < NEL;
+    const int y = node ? x : x - NEL;
+    const int r = y / KH, j = y % KH;
+    const long row = r0 + r;
+    const bool live = row < nrows;
+    const float* __restrict__ in = sIn + r * (KF0 + KFE);
+    float val, xh, rstd;
+    if (node) {
+      const int c = j < KF0 ? j : 0;
+      val = mod1_elem<KF0, 1>(in, sGamN, sBetN, sWN + j * KF0, sBN[j], c, &xh,
+                              &rstd);
+      if (!EDGE && live) {
+        P.hn1[row * KH + j] = val;
+        if (j < KF0) P.xh_z1[row * KF0 + j] = xh;
+        if (j == 0) P.rst_z1[row] = rstd;
+      }
+      sX[r * XS + j] = live ? val : 0.f;
+      if (!EDGE) sX[r * XS + KH + j] = 0.f;
+    } else {
+      const int c = j < KFE ? j : 0;
+      val = mod1_elem<KFE, 0>(in + KF0, sGamE, sBetE, sWE + j * KFE, sBE[j],
+                              c, &xh, &rstd);
+      if (live) {
+        P.he1[row * KH + j] = val;
+        if (j < KFE) P.xh_e1[row * KFE + j] = xh;
+        if (j == 0) P.rst_e1[row] = rstd;
+      }
+      sX[r * XS + KH + j] = live ? val : 0.f;
+    }
+  }
+  __syncthreads();
+  // from here rows_fwd_lanes<KMSG, KHID, EDGE ? 0 : KH, L>'s body
+  constexpr int NF = EDGE ? 0 : KH;
+  float* __restrict__ xhat_out = EDGE ? P.xh_m1e : P.xh_m1s;
+  float* __restrict__ rstd_out = EDGE ? P.rst_m1e : P.rst_m1s;
+  float* __restrict__ out = EDGE ? P.re1 : P.rs1;
+  const int g = tid / L, l = tid % L;
+  const long row = r0 + g;
+  const bool live = row < nrows;
+  const float* __restrict__ x = sX + g * XS;
+  float s = 0.f;
+#pragma unroll 8
+  for (int i = 0; i < KMSG; ++i) s = s + x[i];
+  const float mu = s / KMSG;
+  float var;
+  {
+    const float d0 = x[0] - mu;
+    var = d0 * d0;
+  }
+#pragma unroll 8
+  for (int i = 1; i < KMSG; ++i) {
+    const float d = x[i] - mu;
+    if (i >= KMSG - NF) var = FMA(d, d, var);
+    else var = var + d * d;
+  }
+  const float rstd = rsqrtf(FMA(var, 1.f / KMSG, LN_EPS));
+  for (int i = l; i < KMSG; i += L) {
+    const float xh = (x[i] - mu) * rstd;
+    if (live) xhat_out[row * KMSG + i] = xh;
+    sU[g * XS + i] = FMA(xh, sGam[i], sBet[i]);
+  }
+  if (live && l == 0) rstd_out[row] = rstd;
+  __syncthreads();
+  const float* __restrict__ u = sU + g * XS;
+  for (int o = l; o < KHID; o += L) {
+    const float* __restrict__ w = sW + o * XS;
+    float acc = sB[o];
+#pragma unroll 8
+    for (int i = 0; i < KMSG; ++i) acc = FMA(u[i], w[i], acc);
+    if (live) out[row * KHID + o] = acc > 0.f ? acc : 0.f;
+  }
+}
+
+template <int L>
+__global__ void __launch_bounds__(ROW_NT)
+cs_fwd_stage_mlp1_red1_lanes_kernel(CachedPtrs P, CachedDims D, StagePtrs SP,
+                                    StageDims SD, int stage) {
+  if (stage && blockIdx.x == 0) {
+    cs_stage_body(SP, SD);
+    return;
+  }
+  constexpr int RPB = ROW_NT / L;
+  const int blk = (int)blockIdx.x - stage;
+  const int nbE = (D.E + RPB - 1) / RPB;
+  if (blk < nbE)
+    mlp1_red1_rows<L, true>(P, (long)blk * RPB, D.E);
+  else
+    mlp1_red1_rows<L, false>(P, (long)(blk - nbE) * RPB, D.N);
+}
+
+// ---- cs_bwd_scat1_gu1 + the row jobs of cs_bwd_w ----
+// ghn1 / ghe1 / gu_z1 / gu_e1 are row-local functions of gms1 / gme1, which
+// cs_bwd_reduce_lanes<1> wrote one launch earlier, and only the N1 and E1
+// weight-grad jobs read them: those jobs recompute them per 32-row tile while
+// staging it, so the scatter launch and the weight-grad launch need no
+// grid-wide dependency between them and run as one.  Blocks [0, sg_b) are
+// cs_bwd_scat1_gu1_kernel's (they keep storing the four tensors and C_STATS),
+// then the 6 x WSPLIT row-job blocks; R1, R2, N2 and E2 run wgrad_tiled's
+// loops with the roundings written out (wgrad_tiled_x).
+//
+// wgrad_tiled sits above the contraction pragma; its roundings in
+// cs_bwd_w_kernel's gfx950 ISA (docs/KERNELS.md "Round 8") are the same in
+// all six row jobs:
+//   tU = xh*gam+bet   one FMA
+//   unit chain        full 32-row tile: terms 0-19 fused, 20-31 rounded
+//                     products; partial tile: every term fused; the
+//                     accumulator runs on through a split's tiles
+//   bias sum          plain adds
+//   LN gamma sum      gu*xh rounded, then added; LN beta sum plain adds
+template <int Din, int Dout>
+__device__ __forceinline__ void wgrad_tiled_x(
+    const CachedPtrs& P, int tid, int rows0, int rows1,
+    const float* __restrict__ gpre0, const float* __restrict__ gpre1,
+    const float* __restrict__ xh0, const float* __restrict__ xh1,
+    const float* __restrict__ gu0, const float* __restrict__ gu1,
+    int w_slot, float (*tG)[65], float (*tU)[65], float (*tGU)[65],
+    float (*tXH)[65], int split, float* __restrict__ pout) {
+  const float* __restrict__ gam = WP(w_slot);
+  const float* __restrict__ bet = WP(w_slot + 1);
+  constexpr int UNITS = Din * Dout;
+  constexpr int MYU = (UNITS + ROW_NT - 1) / ROW_NT;
+  float acc[MYU];
+#pragma unroll
+  for (int q = 0; q < MYU; ++q) acc[q] = 0.f;
+  float bacc = 0.f, lacc_w = 0.f, lacc_b = 0.f;
+  const int rows = rows0 + rows1;
+  for (int r0 = split * TILE_K; r0 < rows; r0 += WSPLIT * TILE_K) {
+    const int rt = min(TILE_K, rows - r0);
+    for (int x = tid; x < rt * Dout; x += ROW_NT) {
+      const int t = x / Dout, o = x % Dout;
+      const int r = r0 + t;
+      tG[t][o] = (r < rows0) ? gpre0[(long)r * Dout + o]
+                             : gpre1[(long)(r - rows0) * Dout + o];
+    }
+    for (int x = tid; x < rt * Din; x += ROW_NT) {
+      const int t = x / Din, i = x % Din;
+      const int r = r0 + t;
+      const float xh = (r < rows0) ? xh0[(long)r * Din + i]
+                                   : xh1[(long)(r - rows0) * Din + i];
+      tU[t][i] = FMA(xh, gam[i], bet[i]);
+      tXH[t][i] = xh;
+      tGU[t][i] = (r < rows0) ? gu0[(long)r * Din + i]
+                              : gu1[(long)(r - rows0) * Din + i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) {
+      const int u = tid + q * ROW_NT;
+      if (u < UNITS) {
+        const int o = u / Din, i = u % Din;
+        float a = acc[q];
+        if (rt == TILE_K) {
+#pragma unroll
+          for (int t = 0; t < 20; ++t) a = FMA(tG[t][o], tU[t][i], a);
+#pragma unroll
+          for (int t = 20; t < TILE_K; ++t) a = a + tG[t][o] * tU[t][i];
+        } else {
+          for (int t = 0; t < rt; ++t) a = FMA(tG[t][o], tU[t][i], a);
+        }
+        acc[q] = a;
+      }
+    }
+    if (tid < Dout)
+      for (int t = 0; t < rt; ++t) bacc = bacc + tG[t][tid];
+    if (tid < Din)
+      for (int t = 0; t < rt; ++t) {
+        lacc_w = lacc_w + tGU[t][tid] * tXH[t][tid];
+        lacc_b = lacc_b + tGU[t][tid];
+      }
+    __syncthreads();
+  }
+  // partial layout: [w UNITS][b Dout][ln_w Din][ln_b Din]
+#pragma unroll
+  for (int q = 0; q < MYU; ++q) {
+    const int u = tid + q * ROW_NT;
+    if (u < UNITS) pout[u] = acc[q];
+  }
+  if (tid < Dout) pout[UNITS + tid] = bacc;
+  if (tid < Din) {
+    pout[UNITS + Dout + tid] = lacc_w;
+    pout[UNITS + Dout + Din + tid] = lacc_b;
+  }
+}
+
+// the N1 / E1 jobs: wgrad_tiled_x with tG and tGU recomputed from gms1 / gme1
+template <int Din, bool NODE>
+__device__ __forceinline__ void wgrad_m1_tiled(
+    const CachedPtrs& P, int tid, int rows, int w_slot, float (*tG)[65],
+    float (*tU)[65], float (*tGU)[65], float (*tXH)[65], int split,
+    float* __restrict__ pout) {
+  constexpr int Dout = KH;
+  constexpr int UNITS = Din * Dout;
+  static_assert(UNITS <= ROW_NT, "one unit per thread");
+  __shared__ float sWm[KH * Din];
+  const float* __restrict__ gam = WP(w_slot);
+  const float* __restrict__ bet = WP(w_slot + 1);
+  const float* __restrict__ xhp = NODE ? P.xh_z1 : P.xh_e1;
+  for (int x = tid; x < KH * Din; x += ROW_NT) sWm[x] = WP(w_slot + 2)[x];
+  float acc = 0.f, bacc = 0.f, lacc_w = 0.f, lacc_b = 0.f;
+  for (int r0 = split * TILE_K; r0 < rows; r0 += WSPLIT * TILE_K) {
+    const int rt = min(TILE_K, rows - r0);
+    // tG: cs_bwd_scat1_gu1_kernel's scatter of the tile's rows
+    for (int x = tid; x < rt * Dout; x += ROW_NT) {
+      const int t = x / Dout, o = x % Dout;
+      const long r = r0 + t;
+      float g;
+      if (NODE) {
+        const long lo = P.src_indptr[r], hi = P.src_indptr[r + 1];
+        float a = P.gms1[r * KMSG + o];
+        for (long q = lo; q < hi; ++q)
+          a = a + P.gme1[P.src_order[q] * KMSG + o];
+        g = P.hn1[r * KH + o] > 0.f ? a : 0.f;
+      } else {
+        const float ge = P.gme1[r * KMSG + KH + o];
+        g = P.he1[r * KH + o] > 0.f ? ge : 0.f;
+      }
+      tG[t][o] = g;
+    }
+    for (int x = tid; x < rt * Din; x += ROW_NT) {
+      const int t = x / Din, i = x % Din;
+      const float xh = xhp[(long)(r0 + t) * Din + i];
+      tU[t][i] = FMA(xh, gam[i], bet[i]);
+      tXH[t][i] = xh;
+    }
+    __syncthreads();
+    // tGU: the 16-term chain from 0, all fused
+    for (int x = tid; x < rt * Din; x += ROW_NT) {
+      const int t = x / Din, i = x % Din;
+      float a = 0.f;
+#pragma unroll
+      for (int o = 0; o < KH; ++o) a = FMA(sWm[o * Din + i], tG[t][o], a);
+      tGU[t][i] = a;
+    }
+    __syncthreads();
+    if (tid < UNITS) {
+      const int o = tid / Din, i = tid % Din;
+      float a = acc;
+      if (rt == TILE_K) {
+#pragma unroll
+        for (int t = 0; t < 20; ++t) a = FMA(tG[t][o], tU[t][i], a);
+#pragma unroll
+        for (int t = 20; t < TILE_K; ++t) a = a + tG[t][o] * tU[t][i];
+      } else {
+        for (int t = 0; t < rt; ++t) a = FMA(tG[t][o], tU[t][i], a);
+      }
+      acc = a;
+    }
+    if (tid < Dout)
+      for (int t = 0; t < rt; ++t) bacc = bacc + tG[t][tid];
+    if (tid < Din)
+      for (int t = 0; t < rt; ++t) {
+        lacc_w = lacc_w + tGU[t][tid] * tXH[t][tid];
+        lacc_b = lacc_b + tGU[t][tid];
+      }
+    __syncthreads();
+  }
+  // partial layout: [w UNITS][b Dout][ln_w Din][ln_b Din]
+  if (tid < UNITS) pout[tid] = acc;
+  if (tid < Dout) pout[UNITS + tid] = bacc;
+  if (tid < Din) {
+    pout[UNITS + Dout + tid] = lacc_w;
+    pout[UNITS + Dout + Din + tid] = lacc_b;
+  }
+}
+
+__global__ void __launch_bounds__(ROW_NT)
+cs_bwd_scat1_gu1_w_kernel(CachedPtrs P, CachedDims D) {
+  const int tid = threadIdx.x;
+  const int nbN = (D.N + SG_RPB - 1) / SG_RPB;
+  const int nbE = (D.E + SG_RPB - 1) / SG_RPB;
+  const int sg_b = nbN + nbE + 1;
+  if ((int)blockIdx.x >= sg_b) {
+    __shared__ float tG[TILE_K][65];
+    __shared__ float tU[TILE_K][65];
+    __shared__ float tGU[TILE_K][65];
+    __shared__ float tXH[TILE_K][65];
+    const int blk = (int)blockIdx.x - sg_b;
+    const int job = blk / WSPLIT;
+    const int sp = blk % WSPLIT;
+    float* pout = P.wg_scratch + ((long)job * WSPLIT + sp) * WG_JSTRIDE;
+    switch (job) {
+      case 0:  // node module 1
+        wgrad_m1_tiled<KF0, true>(P, tid, D.N, W_LN_N1_W, tG, tU, tGU, tXH,
+                                  sp, pout);
+        return;
+      case 1:  // edge module 1
+        wgrad_m1_tiled<KFE, false>(P, tid, D.E, W_LN_E1_W, tG, tU, tGU, tXH,
+                                   sp, pout);
+        return;
+      case 2:  // reduce module 1 (edge ++ self rows)
+        wgrad_tiled_x<KMSG, KHID>(P, tid, D.E, D.N, P.gpre1_e, P.gpre1_s,
+                                  P.xh_m1e, P.xh_m1s, P.gu_m1e, P.gu_m1s,
+                                  W_LN_R1_W, tG, tU, tGU, tXH, sp, pout);
+        return;
+      case 3:  // node module 2
+        wgrad_tiled_x<KHID, KH>(P, tid, D.N, 0, P.gpn1, nullptr, P.xh_h2,
+                                nullptr, P.gu_h2, nullptr, W_LN_N2_W, tG, tU,
+                                tGU, tXH, sp, pout);
+        return;
+      case 4:  // edge module 2
+        wgrad_tiled_x<KFE, KH>(P, tid, D.E, 0, P.gpe1, nullptr, P.xh_e2,
+                               nullptr, P.gu_e2, nullptr, W_LN_E2_W, tG, tU,
+                               tGU, tXH, sp, pout);
+        return;
+      default:  // 5: reduce module 2
+        wgrad_tiled_x<KMSG, KOUT>(P, tid, D.E, D.N, P.gpe2, P.gpn2,
+                                  P.xh_m2e, P.xh_m2s, P.gu_m2e, P.gu_m2s,
+                                  W_LN_R2_W, tG, tU, tGU, tXH, sp, pout);
+        return;
+    }
+  }
+  // cs_bwd_scat1_gu1_kernel's blocks, unchanged
+  __shared__ float sWN[KH * KF0], sWE[KH * KFE];
+  __shared__ float sG[SG_RPB][KH + 1];
+  for (int x = tid; x < KH * KF0; x += ROW_NT) sWN[x] = WP(W_N1_W)[x];
+  for (int x = tid; x < KH * KFE; x += ROW_NT) sWE[x] = WP(W_E1_W)[x];
+  const int r = tid / KH, i = tid % KH;
+  if ((int)blockIdx.x >= nbN + nbE) {
+    __shared__ float sT[SG_MAXB][4];
+    __shared__ float sAcc[SG_MAXB / SG_SPB][4];
+    for (int b = tid; b < D.B; b += ROW_NT) {
+      const float logp_a = P.lp[(long)b * KA + P.actions[b]];
+      const float old_lp = P.old_logp[b];
+      const float ratio = __expf(logp_a - old_lp);
+      const float A_b = P.adv[b];
+      const float r_cl = fminf(fmaxf(ratio, 1.f - D.clip), 1.f + D.clip);
+      const float surr1 = ratio * A_b, surr2 = r_cl * A_b;
+      const float verr = P.values[b] - P.vtarg[b];
+      sT[b][0] = -fminf(surr1, surr2);
+      sT[b][1] = fminf(verr * verr, D.vf_clip);
+      sT[b][2] = old_lp - logp_a;
+      sT[b][3] = P.hent[b];
+    }
+    __syncthreads();
+    const int ng = (D.B + SG_SPB - 1) / SG_SPB;
+    for (int x = tid; x < ng * 4; x += ROW_NT) {
+      const int g = x / 4, k = x % 4;
+      const int b_lo = g * SG_SPB;
+      const int nb = min(D.B - b_lo, SG_SPB);
+      float acc = sT[b_lo][k];
+      for (int t = 1; t < nb; ++t) acc = acc + sT[b_lo + t][k];
+      sAcc[g][k] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const float inv = 1.f / D.B;
+      const float klc = P.kl[0];
+      for (int g = 0; g < ng; ++g) {
+        const float pl = sAcc[g][0] * inv;
+        const float vf = sAcc[g][1] * inv;
+        const float kl = sAcc[g][2] * inv;
+        const float ent = sAcc[g][3] * inv;
+        atomicAdd(&P.stats[0], pl);
+        atomicAdd(&P.stats[1], vf);
+        atomicAdd(&P.stats[2], kl);
+        atomicAdd(&P.stats[3], ent);
+        atomicAdd(&P.stats[4],
+                  FMA(-D.ent_coef, ent, FMA(D.vf_coef, vf, FMA(kl, klc, pl))));
+      }
+    }
+  } else if ((int)blockIdx.x < nbN) {
+    const long r0 = (long)blockIdx.x * SG_RPB;
+    const long v = r0 + r;
+    float g = 0.f;
+    if (v < D.N) {
+      const long lo = P.src_indptr[v], hi = P.src_indptr[v + 1];
+      float acc = P.gms1[v * KMSG + i];
+      for (long q = lo; q < hi; ++q)
+        acc = acc + P.gme1[P.src_order[q] * KMSG + i];
+      g = P.hn1[v * KH + i] > 0.f ? acc : 0.f;
+      P.ghn1[v * KH + i] = g;
+    }
+    sG[r][i] = g;
+    __syncthreads();
+    for (int x = tid; x < SG_RPB * KF0; x += ROW_NT) {
+      const int rr = x / KF0, ii = x % KF0;
+      if (r0 + rr < D.N) {
+        float acc = 0.f;
+#pragma unroll
+        for (int o = 0; o < KH; ++o)
+          acc = FMA(sWN[o * KF0 + ii], sG[rr][o], acc);
+        P.gu_z1[(r0 + rr) * KF0 + ii] = acc;
+      }
+    }
+  } else {
+    const long r0 = (long)(blockIdx.x - nbN) * SG_RPB;
+    const long k = r0 + r;
+    float g = 0.f;
+    if (k < D.E) {
+      const float ge = P.gme1[k * KMSG + KH + i];
+      g = P.he1[k * KH + i] > 0.f ? ge : 0.f;
+      P.ghe1[k * KH + i] = g;
+    }
+    sG[r][i] = g;
+    __syncthreads();
+    for (int x = tid; x < SG_RPB * KFE; x += ROW_NT) {
+      const int rr = x / KFE, ii = x % KFE;
+      if (r0 + rr < D.E) {
+        float acc = 0.f;
+#pragma unroll
+        for (int o = 0; o < KH; ++o)
+          acc = FMA(sWE[o * KFE + ii], sG[rr][o], acc);
+        P.gu_e1[(r0 + rr) * KFE + ii] = acc;
+      }
+    }
+  }
+}
+
 // ===========================================================================
 // host bindings
 // ===========================================================================
@@ -2770,12 +3322,20 @@ cs_fwd_stage_mlp1_lanes_kernel(CachedPtrs P, CachedDims D, StagePtrs SP,
 //                                of cs_bwd_w as launches / blocks of their
 //                                own (oracle / A/B); STEP_FUSION=off and
 //                                'thread' imply it
+//   DDLS_AMD_STEP_MERGE=off      cs_fwd_stage_mlp1_lanes + cs_fwd_reduce_lanes<1>
+//                                and cs_bwd_scat1_gu1 + cs_bwd_w as two
+//                                launches each, and cs_bwd_w_reduce always
+//                                launched by cached_step_bwd (oracle / A/B);
+//                                STEP_OVERLAP=off, STEP_FUSION=off and
+//                                'thread' imply it
 struct RowCfg {
   bool thread;
   int lanes;   // 0: per-kernel default
   bool fused;  // the fused launches (needs the lane-parallel row kernels)
   bool overlap;  // independent work rides in launches that exist anyway
                  // (needs the fused launches)
+  bool merge;    // launches merged along row-local dependencies (needs
+                 // overlap)
 };
 
 static RowCfg row_cfg() {
@@ -2806,6 +3366,12 @@ static RowCfg row_cfg() {
               "cached_step: DDLS_AMD_STEP_OVERLAP must be 'on' or 'off', got '",
               so, "'");
   c.overlap = !ooff && c.fused;
+  const char* sm = getenv("DDLS_AMD_STEP_MERGE");
+  const bool moff = (sm != nullptr && strcmp(sm, "off") == 0);
+  TORCH_CHECK(sm == nullptr || sm[0] == '\0' || moff || strcmp(sm, "on") == 0,
+              "cached_step: DDLS_AMD_STEP_MERGE must be 'on' or 'off', got '",
+              sm, "'");
+  c.merge = !moff && c.overlap;
   return c;
 }
 
@@ -2977,6 +3543,29 @@ static void step_fwd_launches(const CachedPtrs& P, const CachedDims& D,
                        stream, P, D);
     hipLaunchKernelGGL(cs_fwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
+  } else if (R.merge) {
+    // stage role (with a store) + round-1 modules + round-1 reduce module
+    const int L_ = R.lanes ? R.lanes : 32;
+    const int rpb_ = ROW_NT / L_;
+    const int stage = SP != nullptr ? 1 : 0;
+    const dim3 grid(stage + (D.E + rpb_ - 1) / rpb_ + (D.N + rpb_ - 1) / rpb_);
+    StagePtrs sp0;
+    StageDims sd0;
+    memset(&sp0, 0, sizeof(sp0));
+    memset(&sd0, 0, sizeof(sd0));
+    const StagePtrs& sp = stage ? *SP : sp0;
+    const StageDims& sd = stage ? *SD : sd0;
+    if (grid.x > 0) {
+      if (L_ == 8)
+        hipLaunchKernelGGL(cs_fwd_stage_mlp1_red1_lanes_kernel<8>, grid,
+                           dim3(ROW_NT), 0, stream, P, D, sp, sd, stage);
+      else if (L_ == 16)
+        hipLaunchKernelGGL(cs_fwd_stage_mlp1_red1_lanes_kernel<16>, grid,
+                           dim3(ROW_NT), 0, stream, P, D, sp, sd, stage);
+      else
+        hipLaunchKernelGGL(cs_fwd_stage_mlp1_red1_lanes_kernel<32>, grid,
+                           dim3(ROW_NT), 0, stream, P, D, sp, sd, stage);
+    }
   } else {
     if (SP != nullptr) {
       const int L_ = R.lanes ? R.lanes : 16;
@@ -3071,7 +3660,47 @@ void cached_step_fwd_staged(std::vector<torch::Tensor> T,
   step_fwd_launches(P, D, R, &SP, &SD);
 }
 
-void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
+// defer_reduce: leave the row jobs' partial sums in wg_scratch for the folded
+// optimiser tail (flat_sumsq_adam_folded), which then forms flat_g's row-job
+// segments itself.  Ignored unless the merge switch is on and the row jobs
+// are split (not with DDLS_AMD_WGRAD_MFMA=1); cached_step_reduce_deferred()
+// tells the caller.  Default: flat_g is complete when this returns.
+bool cached_step_reduce_deferred(bool defer_reduce) {
+  const char* wm = getenv("DDLS_AMD_WGRAD_MFMA");
+  const bool mfma = (wm != nullptr && wm[0] == '1');
+  return defer_reduce && row_cfg().merge && !mfma;
+}
+
+// The row jobs' gradient segments for the folded tail: for each of the 24
+// (job, tensor) pairs the flat start, the length and the offset of split 0's
+// partial in wg_scratch (cs_bwd_w_reduce_kernel's layout: W, b, LN gamma, LN
+// beta), then WSPLIT and WG_JSTRIDE.  offs is the host copy of C_OFFS.
+std::vector<int64_t> cached_step_fold_segments(std::vector<int64_t> offs) {
+  TORCH_CHECK((int)offs.size() == W_COUNT, "cached_step_fold_segments: ",
+              (int)W_COUNT, " slot offsets expected, got ", offs.size());
+  const int din[6] = {KF0, KFE, KMSG, KHID, KFE, KMSG};
+  const int dout[6] = {KH, KH, KHID, KH, KH, KOUT};
+  const int slot[6] = {W_LN_N1_W, W_LN_E1_W, W_LN_R1_W,
+                       W_LN_N2_W, W_LN_E2_W, W_LN_R2_W};
+  std::vector<int64_t> segs;
+  for (int j = 0; j < 6; ++j) {
+    const int64_t base = (int64_t)j * WSPLIT * WG_JSTRIDE;
+    const int64_t units = (int64_t)din[j] * dout[j];
+    const int64_t quad[4][3] = {
+        {offs[slot[j] + 2], units, base},
+        {offs[slot[j] + 3], dout[j], base + units},
+        {offs[slot[j]], din[j], base + units + dout[j]},
+        {offs[slot[j] + 1], din[j], base + units + dout[j] + din[j]}};
+    for (int q = 0; q < 4; ++q)
+      for (int c = 0; c < 3; ++c) segs.push_back(quad[q][c]);
+  }
+  segs.push_back(WSPLIT);
+  segs.push_back(WG_JSTRIDE);
+  return segs;
+}
+
+void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs,
+                     bool defer_reduce) {
   CachedPtrs P;
   CachedDims D;
   RowCfg R;
@@ -3114,6 +3743,19 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
       LAUNCH_ROWS(K_BWD_MLP2, 16, D.N, D.E);
     LAUNCH_ROWS(K_BWD_RED1, 32, D.E, D.N);
   }
+  const int nsplit = D.wgrad_mfma ? 1 : WSPLIT;
+  if (R.merge && nsplit > 1 && D.B > 0) {
+    // the scatter's row blocks and statistics block, then the 6 x WSPLIT
+    // row-job blocks, in one launch
+    const int sg_b = (D.N + SG_RPB - 1) / SG_RPB + (D.E + SG_RPB - 1) / SG_RPB
+                     + 1;
+    hipLaunchKernelGGL(cs_bwd_scat1_gu1_w_kernel, dim3(sg_b + 6 * WSPLIT),
+                       dim3(ROW_NT), 0, stream, P, D);
+    if (!defer_reduce)
+      hipLaunchKernelGGL(cs_bwd_w_reduce_kernel, dim3(6), dim3(256), 0,
+                         stream, P, D);
+    return;
+  }
   if (R.fused) {
     // row blocks, then the loss-statistics block
     const int sg_b = (D.N + SG_RPB - 1) / SG_RPB + (D.E + SG_RPB - 1) / SG_RPB
@@ -3137,14 +3779,13 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
       hipLaunchKernelGGL(cs_bwd_gu1_lanes_kernel, dim3(gu1_b), dim3(ROW_NT),
                          0, stream, P, D);
   }
-  const int nsplit = D.wgrad_mfma ? 1 : WSPLIT;
   // 6 row jobs x nsplit, the graph-module block, 16 FC-column blocks; in
   // overlap mode the 17 B-row blocks ran in cs_bwd_pool_wfc above, and with
   // the row-job grid their paths are never entered
   hipLaunchKernelGGL(cs_bwd_w_kernel,
                      dim3(6 * nsplit + (R.overlap ? 0 : 1 + 16)), dim3(256),
                      0, stream, P, D);
-  if (nsplit > 1)
+  if (nsplit > 1 && !(defer_reduce && R.merge))
     hipLaunchKernelGGL(cs_bwd_w_reduce_kernel, dim3(6), dim3(256), 0,
                        stream, P, D);
 }

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <cstring>
 #include <vector>
 
 #define WAVE 64
@@ -802,4 +803,144 @@ void flat_sumsq_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
 int64_t flat_sumsq_blocks(int64_t numel) {
     long sblocks = (numel + BLOCK - 1) / BLOCK;
     return sblocks > SUMSQ_MAX_BLOCKS ? SUMSQ_MAX_BLOCKS : sblocks;
+}
+
+// ---------------------------------------------------------------------------
+// The optimiser tail with the row-split weight-grad reduce folded in.
+// cached_step_bwd can leave the six row jobs' partial sums in wg_scratch
+// (cs_bwd_w_reduce's launch goes away); K1 below then forms each of those
+// gradient elements itself: thread i of sumsq_partials' grid looks flat index
+// i up in the segment table (passed by value), and if it lies in a row-job
+// segment adds the nsplit partials from 0 in split order — the sequence
+// cs_bwd_w_reduce_kernel runs — stores flat_g[i] and squares it in
+// sumsq_partials' own chain.  K2 is flat_adam_partials, unchanged.
+//
+// Contraction is off from here on and the roundings are written out as the
+// gfx950 ISA of the two kernels this one replaces has them: the reduce is
+// plain adds (it has no products), and sumsq's per-thread chain is one fused
+// multiply-add per element, s = fma(x, x, s); the wave and block sums are
+// plain adds.
+#pragma clang fp contract(off)
+
+#define FOLD_MAX_SEGS 24
+#define FOLD_NSPLIT 16
+
+struct FoldSegs {
+    int nseg;
+    int stride;                  // floats between two splits of one job
+    int start[FOLD_MAX_SEGS];    // first flat index of the segment
+    int len[FOLD_MAX_SEGS];
+    int soff[FOLD_MAX_SEGS];     // split 0's offset of the segment in scratch
+};
+
+__global__ void __launch_bounds__(BLOCK)
+sumsq_partials_folded_kernel(float* __restrict__ g,
+                             const float* __restrict__ scratch, FoldSegs S,
+                             float* __restrict__ partials, float* step_t,
+                             long n) {
+    __shared__ float part[WAVES_PER_BLOCK];
+    const int wave = threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    float s = 0.0f;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n;
+         i += (long)gridDim.x * BLOCK) {
+        long so = -1;
+        for (int q = 0; q < S.nseg; ++q) {
+            const long d = i - S.start[q];
+            if (d >= 0 && d < S.len[q]) so = S.soff[q] + d;
+        }
+        float x;
+        if (so >= 0) {
+            float pv[FOLD_NSPLIT];
+#pragma unroll
+            for (int k = 0; k < FOLD_NSPLIT; ++k)
+                pv[k] = scratch[so + (long)k * S.stride];
+            float a = 0.0f;
+#pragma unroll
+            for (int k = 0; k < FOLD_NSPLIT; ++k) a = a + pv[k];
+            g[i] = a;
+            x = a;
+        } else {
+            x = g[i];
+        }
+        s = __builtin_fmaf(x, x, s);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        s = s + __shfl_down(s, off, WAVE);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+        for (int w = 0; w < WAVES_PER_BLOCK; ++w) t = t + part[w];
+        partials[blockIdx.x] = t;
+        if (blockIdx.x == 0) step_t[0] = step_t[0] + 1.0f;
+    }
+}
+
+// segs = nseg x (flat start, length, scratch offset of split 0), as
+// cached_step_fold_segments() returns them; host data, so nothing is read
+// from the device while a graph is being captured
+void flat_sumsq_adam_folded(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                            torch::Tensor v, torch::Tensor step_t,
+                            torch::Tensor normsq, torch::Tensor partials,
+                            torch::Tensor scratch, std::vector<int64_t> segs,
+                            int64_t nsplit, int64_t stride, double clip,
+                            double lr, double b1, double b2, double eps) {
+    const long numel = p.numel();
+    TORCH_CHECK(g.numel() == numel && m.numel() == numel
+                && v.numel() == numel,
+                "flat_sumsq_adam_folded: size mismatch");
+    TORCH_CHECK(scratch.is_cuda() && scratch.is_contiguous()
+                && scratch.scalar_type() == torch::kFloat32
+                && scratch.device() == g.device(),
+                "flat_sumsq_adam_folded: scratch must be a contiguous f32 "
+                "tensor on the gradient's device");
+    TORCH_CHECK(nsplit == FOLD_NSPLIT, "flat_sumsq_adam_folded: compiled for ",
+                FOLD_NSPLIT, " splits, got ", nsplit);
+    TORCH_CHECK(segs.size() % 3 == 0
+                && segs.size() / 3 <= (size_t)FOLD_MAX_SEGS,
+                "flat_sumsq_adam_folded: at most ", FOLD_MAX_SEGS,
+                " (start, len, offset) segments");
+    TORCH_CHECK(stride > 0 && stride < (1L << 30) && numel < (1L << 31),
+                "flat_sumsq_adam_folded: stride / numel out of range");
+    FoldSegs S;
+    memset(&S, 0, sizeof(S));
+    S.nseg = (int)(segs.size() / 3);
+    S.stride = (int)stride;
+    for (int q = 0; q < S.nseg; ++q) {
+        const int64_t st = segs[3 * q], ln = segs[3 * q + 1],
+                      so = segs[3 * q + 2];
+        TORCH_CHECK(st >= 0 && ln >= 0 && st + ln <= numel,
+                    "flat_sumsq_adam_folded: segment ", q,
+                    " outside the flat buffer");
+        TORCH_CHECK(so >= 0
+                    && so + (nsplit - 1) * stride + ln <= scratch.numel(),
+                    "flat_sumsq_adam_folded: segment ", q,
+                    " outside the scratch buffer");
+        S.start[q] = (int)st;
+        S.len[q] = (int)ln;
+        S.soff[q] = (int)so;
+    }
+    long sblocks = (numel + BLOCK - 1) / BLOCK;
+    if (sblocks > SUMSQ_MAX_BLOCKS) sblocks = SUMSQ_MAX_BLOCKS;
+    TORCH_CHECK(partials.numel() >= sblocks,
+                "flat_sumsq_adam_folded: partials buffer holds ",
+                partials.numel(), " floats, needs ", sblocks);
+    if (numel == 0) return;
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL(sumsq_partials_folded_kernel, dim3((int)sblocks),
+                       dim3(BLOCK), 0, stream, g.data_ptr<float>(),
+                       scratch.data_ptr<float>(), S,
+                       partials.data_ptr<float>(), step_t.data_ptr<float>(),
+                       numel);
+    long blocks = (numel + BLOCK - 1) / BLOCK;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(flat_adam_partials_kernel, dim3((int)blocks),
+                       dim3(BLOCK), 0, stream, p.data_ptr<float>(),
+                       g.data_ptr<float>(), m.data_ptr<float>(),
+                       v.data_ptr<float>(), step_t.data_ptr<float>(),
+                       partials.data_ptr<float>(), normsq.data_ptr<float>(),
+                       (int)sblocks, numel, (float)clip, (float)lr, (float)b1,
+                       (float)b2, (float)eps);
 }

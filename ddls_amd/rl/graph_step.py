@@ -58,6 +58,18 @@ def step_overlap_enabled() -> bool:
     return v != "off" and step_fusion_enabled()
 
 
+def step_merge_enabled() -> bool:
+    """Mirror of cached_step.hip's DDLS_AMD_STEP_MERGE switch (default on):
+    the row-split weight-grad reduce may be left to the folded optimiser
+    tail.  It needs the overlap launches, so whatever turns those off turns
+    this off too."""
+    v = os.environ.get("DDLS_AMD_STEP_MERGE", "")
+    if v not in ("", "on", "off"):
+        raise RuntimeError(
+            f"DDLS_AMD_STEP_MERGE must be 'on' or 'off', got '{v}'")
+    return v != "off" and step_overlap_enabled()
+
+
 class _PPOLossFn(torch.autograd.Function):
     """Fused PPO loss (ops/hip/ppo_loss.hip): one kernel forward, one kernel
     analytic backward — replaces ~100 tiny elementwise kernels per replay."""
@@ -169,8 +181,10 @@ class _FusedCachedEngine:
         for name, p in policy.named_parameters():
             name_to_off[name] = off
             off += p.numel()
-        offs = torch.tensor([name_to_off[n] for n in self._SLOTS],
-                            dtype=torch.int64, device=dev)
+        # host copy of the slot offsets: the folded tail's segment table is
+        # built from it, never from the device tensor (capture-safe)
+        self.offs_host = [int(name_to_off[n]) for n in self._SLOTS]
+        offs = torch.tensor(self.offs_host, dtype=torch.int64, device=dev)
 
         H = cfg["out_features_msg"] // 2
         HID = cfg["out_features_hidden"]
@@ -222,10 +236,19 @@ class _FusedCachedEngine:
                       float(c.vf_loss_coeff), float(c.entropy_coeff)]
         self.ext = ext
 
-    def run(self, store=None):
+    def fold_segments(self):
+        """(segs, nsplit, stride) of the six row jobs for
+        ``flat_sumsq_adam_folded``."""
+        t = list(self.ext.cached_step_fold_segments(self.offs_host))
+        return t[:-2], int(t[-2]), int(t[-1])
+
+    def run(self, store=None, defer_reduce=False):
         """One fwd+bwd.  With a ``DeviceBatchStore`` the minibatch is gathered
         from it first: inside the first forward launch when the overlap
-        switch is on, by the stage kernel's own launch otherwise."""
+        switch is on, by the stage kernel's own launch otherwise.  With
+        ``defer_reduce`` the row-split weight-grad partials stay in the
+        scratch buffer and ``flat_g`` is complete only after the folded
+        optimiser tail; the default leaves a complete ``flat_g``."""
         if store is not None and step_overlap_enabled():
             self.ext.cached_step_fwd_staged(
                 self.scratch, self.fscal, store.tensors(), store.perm,
@@ -234,7 +257,10 @@ class _FusedCachedEngine:
             if store is not None:
                 store.stage_into(self.ext, self.st.d)
             self.ext.cached_step_fwd(self.scratch, self.fscal)
-        self.ext.cached_step_bwd(self.scratch, self.fscal)
+        if defer_reduce:
+            self.ext.cached_step_bwd(self.scratch, self.fscal, True)
+        else:
+            self.ext.cached_step_bwd(self.scratch, self.fscal)
 
 
 class DeviceBatchStore:
@@ -750,6 +776,11 @@ class CapturedSGDStep:
 
     # ------------------------------------------------------------------
     _fused_cached = None
+    # the step is captured whole with the merge switch on: _body_fwd_bwd
+    # defers the row-split weight-grad reduce and _body_opt runs the folded
+    # tail.  Decided in _capture; never with a distributed (split) capture,
+    # whose all-reduce needs a complete flat_g in between.
+    _fold_tail = False
 
     def _body_fwd_bwd(self):
         cfg, B = self.cfg, self.B
@@ -758,7 +789,8 @@ class CapturedSGDStep:
             # batch store the gather of this minibatch's rows rides in the
             # first forward launch (DDLS_AMD_STEP_OVERLAP=off: the stage
             # kernel's own launch in front, as below)
-            self._fused_cached.run(self.store)
+            # (_fold_tail: cs_bwd_w_reduce's work is done by the tail)
+            self._fused_cached.run(self.store, defer_reduce=self._fold_tail)
             return
         if self.store is not None:
             # first node of the chain: gather this minibatch's rows from the
@@ -856,6 +888,16 @@ class CapturedSGDStep:
             # in-house sumsq kernel: torch reductions drift under replay)
             hyper = (float(self.cfg.grad_clip or 0.0), float(self.cfg.lr),
                      0.9, 0.999, 1e-8)
+            if self._fold_tail:
+                # the same two launches, the first of which also sums the
+                # row-split weight-grad partials _body_fwd_bwd left behind
+                segs, nsplit, stride = self._fused_cached.fold_segments()
+                self._ext.flat_sumsq_adam_folded(
+                    self.flat_p, self.flat_g, self.flat_m, self.flat_v,
+                    self.step_t, self.normsq, self.normsq_partials,
+                    self._fused_cached.scratch[-1], segs, nsplit, stride,
+                    *hyper)
+                return
             if step_fusion_enabled():
                 # two launches: block partials of the norm (+ the step
                 # count), then their fixed-order sum + clip + Adam
@@ -970,6 +1012,11 @@ class CapturedSGDStep:
                     and _FusedCachedEngine.eligible(self.policy, self._ext)):
                 self._fused_cached = _FusedCachedEngine(self,
                                                         self.models_batch)
+            self._fold_tail = bool(
+                self._fused_cached is not None and not split
+                and step_merge_enabled()
+                and hasattr(self._ext, "flat_sumsq_adam_folded")
+                and self._ext.cached_step_reduce_deferred(True))
             # warmup (required before capture) runs REAL steps; snapshot the
             # flat training state and restore it in place afterwards so the
             # captured graph sees the live tensors but training resumes
