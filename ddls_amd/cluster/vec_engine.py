@@ -900,13 +900,19 @@ def cpu_step_env(spec: EngineSpec, st: EngineState, b: int,
     # throughput family on that step's info_processed/step_time — which the
     # event loop below accrues tick by tick)
     r = spec.reward
-    reward = 0.0
-    if r.jct_weight != 0.0:
-        norm_seq = (spec.mds[mdi].pj_seq if placed else seq_jct)
-        reward += r.jct_weight * _jct_reward(spec, jct_total, seq_jct,
-                                             not placed, norm_seq)
-    if r.blocking_weight != 0.0:
-        reward += r.blocking_weight * (r.acc_success if placed else r.acc_fail)
+
+    def decision_reward(as_placed: bool) -> float:
+        rew = 0.0
+        if r.jct_weight != 0.0:
+            norm_seq = (spec.mds[mdi].pj_seq if as_placed else seq_jct)
+            rew += r.jct_weight * _jct_reward(spec, jct_total, seq_jct,
+                                              not as_placed, norm_seq)
+        if r.blocking_weight != 0.0:
+            rew += r.blocking_weight * (r.acc_success if as_placed
+                                        else r.acc_fail)
+        return rew
+
+    reward = decision_reward(placed)
     st.ep_len[b] += 1
     tp_acc = 0.0
     tp_time = None          # set when the first cluster step closes
@@ -980,6 +986,14 @@ def cpu_step_env(spec: EngineSpec, st: EngineState, b: int,
             tp_time = float(st.t[b]) - t_step_start
         if st.queued[b] >= 0 or done:
             break
+
+    if done and placed and any(int(st.slot_sched[b, s]) == k
+                               for s in range(int(st.n_running[b]))):
+        # the env extracts the reward AFTER cluster.step: a job placed on the
+        # episode's last step that is still running when the episode ends
+        # has by then been blocked at finalisation (below), so the reward
+        # function finds it in jobs_blocked and pays the fail reward
+        reward = decision_reward(False)
 
     if r.tp_kind:
         step_time = (tp_time if tp_time is not None
@@ -1203,6 +1217,10 @@ class CpuEngine:
             "obs_gf": torch.from_numpy(st.obs_gf),
             "obs_mask": torch.from_numpy(st.obs_mask),
             "obs_model": torch.from_numpy(st.obs_model),
+            "obs_sched": torch.from_numpy(st.obs_sched),
+            "model_seq": torch.as_tensor(
+                np.array([ms.seq_total for ms in spec.models],
+                         dtype=np.float64)),
             "reward": torch.from_numpy(st.reward),
             "tp_info": torch.from_numpy(st.tp_info),
             "tp_time": torch.from_numpy(st.tp_time),

@@ -99,6 +99,14 @@ std::vector<torch::Tensor> lookahead_batch(
     torch::Tensor dep_channel, torch::Tensor dep_priority, torch::Tensor dep_dst,
     torch::Tensor dep_ready, torch::Tensor dep_completed,
     torch::Tensor worker_best, torch::Tensor channel_best);
+void actor_batch(torch::Tensor obs_gf, torch::Tensor obs_mask,
+                 torch::Tensor obs_model, torch::Tensor obs_sched,
+                 torch::Tensor done, torch::Tensor model_emb,
+                 std::vector<torch::Tensor> head, torch::Tensor model_seq,
+                 torch::Tensor sch_acc, int64_t mode, int64_t sip_ml_cap,
+                 uint64_t seed, uint64_t step, torch::Tensor actions,
+                 torch::Tensor gfull, torch::Tensor lp_all,
+                 torch::Tensor logp, torch::Tensor value, torch::Tensor u);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("row_mlp", &row_mlp, "fused LN+Linear+ReLU over rows");
@@ -161,4 +169,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("env_step_batch", &env_step_batch,
           "batched RAMP env step over vectorised envs (placement search + "
           "memo hash probe + event loop + obs encode)");
+    m.def("actor_batch", &actor_batch,
+          "device-side actors over vectorised envs: GNN policy head (greedy "
+          "or Philox-sampled) and the six heuristic baselines, one launch");
 }

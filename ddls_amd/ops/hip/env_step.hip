@@ -508,6 +508,22 @@ env_step_kernel(EnvPtrs P, EnvDims D) {
     if (P.queued[b] >= 0 || done) break;
   }
 
+  if (done && placed) {
+    // the env extracts the reward after cluster.step: a job placed on the
+    // episode's last step that is still running at the end has by then been
+    // blocked at finalisation (below) and is paid the fail reward
+    bool still_running = false;
+    for (int s = 0; s < P.n_running[b]; ++s)
+      if (P.slot_sched[(long)b * D.K + s] == k) still_running = true;
+    if (still_running) {
+      reward = 0.0;
+      if (D.r_jct_w != 0.0)
+        reward += D.r_jct_w * jct_reward(D, jct_total, seq_jct, true,
+                                         seq_jct);
+      if (D.r_blk_w != 0.0) reward += D.r_blk_w * D.r_acc_fail;
+    }
+  }
+
   if (D.r_tp_kind != 0) {
     double step_time = tp_closed ? tp_time : P.t[b] - t_start;
     reward = (tp_acc != 0.0 && step_time != 0.0) ? tp_acc / step_time : 0.0;

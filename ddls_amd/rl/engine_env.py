@@ -59,11 +59,32 @@ class LazyObsSeq:
         return iter(self._materialise())
 
 
+def build_models_batch(spec, device) -> GraphBatch:
+    """One flat GraphBatch holding every model's (static) graph."""
+    nfs = [ms.node_features for ms in spec.models]
+    z = np.concatenate(nfs)
+    e = np.concatenate([ms.edge_features for ms in spec.models])
+    ns = np.array([nf.shape[0] for nf in nfs], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(ns)[:-1]])
+    src = np.concatenate([ms.edges_src + o
+                          for ms, o in zip(spec.models, offs)])
+    dst = np.concatenate([ms.edges_dst + o
+                          for ms, o in zip(spec.models, offs)])
+    gid = np.repeat(np.arange(len(ns), dtype=np.int64), ns)
+    t = lambda a, dt: torch.as_tensor(a, device=device, dtype=dt)
+    return GraphBatch(z=t(z, torch.float32), e=t(e, torch.float32),
+                      src=t(src, torch.int64), dst=t(dst, torch.int64),
+                      graph_of_node=t(gid, torch.int64),
+                      num_graphs=len(ns))
+
+
 class EngineVectorEnv:
     """Same trainer-facing API as SubprocVectorEnv, GPU-resident."""
 
     # rollout() takes device_resident=True (PPOTrainer's device-batch path)
     supports_device_resident = True
+    # rollout() takes sampler="device" (one actor_batch launch per step)
+    supports_device_sampler = True
 
     def __init__(self, env_fn, num_envs: int, device, base_seed: int = 0,
                  spec=None, proto_env=None, verbose: bool = False):
@@ -95,6 +116,9 @@ class EngineVectorEnv:
         for b in range(num_envs):
             self.eng.reset_env(b, self.scheds[b])
         self.completed_episode_stats: List[dict] = []
+        # Philox step counter of the device sampler: never reused, so every
+        # (env, step) of this env's lifetime draws its own uniform
+        self._sampler_step = 0
         # per-model static tensors for collate-at-update + embedding cache
         self._model_nf = [ms.node_features for ms in spec.models]
         self._model_ef = [ms.edge_features for ms in spec.models]
@@ -116,19 +140,7 @@ class EngineVectorEnv:
 
     def _build_models_batch(self) -> GraphBatch:
         """One flat GraphBatch holding every model's (static) graph."""
-        dev = self.device
-        z = np.concatenate(self._model_nf)
-        e = np.concatenate(self._model_ef)
-        ns = np.array([nf.shape[0] for nf in self._model_nf], dtype=np.int64)
-        offs = np.concatenate([[0], np.cumsum(ns)[:-1]])
-        src = np.concatenate([s + o for s, o in zip(self._model_src, offs)])
-        dst = np.concatenate([d + o for d, o in zip(self._model_dst, offs)])
-        gid = np.repeat(np.arange(len(ns), dtype=np.int64), ns)
-        t = lambda a, dt: torch.as_tensor(a, device=dev, dtype=dt)
-        return GraphBatch(z=t(z, torch.float32), e=t(e, torch.float32),
-                          src=t(src, torch.int64), dst=t(dst, torch.int64),
-                          graph_of_node=t(gid, torch.int64),
-                          num_graphs=len(ns))
+        return build_models_batch(self.spec, self.device)
 
     def __len__(self):
         return self.num_envs
@@ -170,12 +182,21 @@ class EngineVectorEnv:
         return logits, value
 
     @torch.no_grad()
-    def rollout(self, policy, steps: int,
-                device_resident: bool = False) -> Dict[str, np.ndarray]:
+    def rollout(self, policy, steps: int, device_resident: bool = False,
+                sampler: str = "torch") -> Dict[str, np.ndarray]:
         """``device_resident=True`` keeps the per-sample training inputs as
         flat ``[T*B, ...]`` tensors on the engine's device (keys ``*_dev``)
         and returns ``obs`` as a LazyObsSeq instead of building T*B
-        CompactObs; sampling and everything GAE needs are unchanged."""
+        CompactObs; sampling and everything GAE needs are unchanged.
+
+        ``sampler="device"`` replaces the per-step torch head + Categorical
+        with one DeviceActor call in POLICY_SAMPLE mode (on a GpuEngine one
+        ``actor_batch`` launch) that writes row ``t`` of the buffers directly;
+        its Philox key is ``base_seed`` and its step counter lives on the
+        env.  The returned dict has the same keys, shapes and dtypes."""
+        if sampler not in ("torch", "device"):
+            raise ValueError("rollout sampler must be 'torch' or 'device', "
+                             f"not {sampler!r}")
         dev = self.device
         B = self.num_envs
         A = self.spec.A
@@ -194,22 +215,40 @@ class EngineVectorEnv:
         buf_rewards = torch.empty((T, B), device=dev)
         buf_dones = torch.empty((T, B), dtype=torch.bool, device=dev)
 
+        actor = None
+        if sampler == "device":
+            from .device_actor import DeviceActor
+            actor = DeviceActor.policy(policy, deterministic=False,
+                                       seed=self.base_seed)
+            actor.prepare(self, model_emb=model_emb)
+            buf_u = torch.empty((T, B), device=dev)
+
         for t in range(T):
-            gf = eng.T["obs_gf"]
-            mask = eng.T["obs_mask"]
-            gfull = torch.cat([gf, mask], dim=1)
-            obs_model = eng.T["obs_model"].long()
-            logits, value = self._head_forward(policy, model_emb, obs_model,
-                                               gfull, mask)
-            dist = torch.distributions.Categorical(logits=logits)
-            actions = dist.sample()
-            buf_gfull[t] = gfull
-            buf_model[t] = obs_model
-            buf_actions[t] = actions
-            buf_lp_all[t] = dist.logits   # normalized log-probs (Categorical)
-            buf_logp[t] = dist.log_prob(actions)
-            buf_values[t] = value
-            eng.step(actions)          # syncs status internally
+            if actor is not None:
+                buf_model[t] = eng.T["obs_model"]
+                actions = actor.act(eng, self._sampler_step, rows={
+                    "gfull": buf_gfull[t], "lp_all": buf_lp_all[t],
+                    "logp": buf_logp[t], "value": buf_values[t],
+                    "u": buf_u[t]})
+                self._sampler_step += 1
+                buf_actions[t] = actions
+                eng.step(actions)
+            else:
+                gf = eng.T["obs_gf"]
+                mask = eng.T["obs_mask"]
+                gfull = torch.cat([gf, mask], dim=1)
+                obs_model = eng.T["obs_model"].long()
+                logits, value = self._head_forward(policy, model_emb,
+                                                   obs_model, gfull, mask)
+                dist = torch.distributions.Categorical(logits=logits)
+                actions = dist.sample()
+                buf_gfull[t] = gfull
+                buf_model[t] = obs_model
+                buf_actions[t] = actions
+                buf_lp_all[t] = dist.logits   # normalized log-probs
+                buf_logp[t] = dist.log_prob(actions)
+                buf_values[t] = value
+                eng.step(actions)      # syncs status internally
             buf_rewards[t] = eng.T["reward"].float()
             done = eng.T["done"] != 0
             buf_dones[t] = done

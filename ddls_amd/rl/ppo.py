@@ -48,6 +48,11 @@ class PPOConfig:
     # says so on stderr when it has to fall back, "off" is the host-staged
     # path exactly.  DDLS_AMD_DISABLE_DEVICE_BATCH=1 forces "off".
     device_batch: str = "auto"
+    # how the engine env samples actions during rollouts: "torch" (head +
+    # Categorical per step) or "device" (rl/device_actor.py: one actor_batch
+    # launch per step).  Forwarded only when it is not "torch" and the env
+    # advertises supports_device_sampler.
+    rollout_sampler: str = "torch"
 
 
 class PPOTrainer:
@@ -121,11 +126,15 @@ class PPOTrainer:
         if hasattr(self.env, "rollout"):
             # RLlib-style worker-side rollouts: policy copies live in the env
             # workers; one IPC round trip per iteration
+            kw = {}
+            if (cfg.rollout_sampler != "torch"
+                    and getattr(self.env, "supports_device_sampler", False)):
+                kw["sampler"] = cfg.rollout_sampler
             if self._device_batch_wanted():
                 data = self.env.rollout(self.policy, steps,
-                                        device_resident=True)
+                                        device_resident=True, **kw)
             else:
-                data = self.env.rollout(self.policy, steps)
+                data = self.env.rollout(self.policy, steps, **kw)
             self.total_env_steps += steps * n_envs
             rewards, dones = data["rewards"], data["dones"]
             values, logps, actions = data["values"], data["logp"], data["actions"]

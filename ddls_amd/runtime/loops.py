@@ -71,6 +71,112 @@ class EvalLoop:
         return results
 
 
+class EngineEvalLoop:
+    """``EvalLoop`` over many seeds at once on the vectorised env engine.
+
+    One env per seed: env b plays ``drain_episode_schedule(gen, spec,
+    seed=seeds[b])``, the episode ``env.reset(seed=seeds[b])`` plays, with a
+    ``rl.device_actor.DeviceActor`` acting for the whole batch per step (one
+    launch on a ``GpuEngine``).  Nothing is reset: finished envs stay done
+    and the engine skips them.  More seeds than ``num_envs`` run in waves.
+
+    ``run(seeds)`` returns one dict per seed with ``EvalLoop.run``'s keys
+    plus ``seed``.  ``episode_return`` is the f64 sum of ``T["reward"]`` in
+    step order over the steps the env was live for (a skipped env keeps a
+    stale reward) — not the engine's own ``ep_return``.
+    """
+
+    def __init__(self, actor, env_fn, device, num_envs: Optional[int] = None,
+                 max_steps: int = 100000, spec=None, proto_env=None):
+        import torch
+        from ..cluster.vec_engine import compile_engine_spec
+        from ..rl.engine_env import build_models_batch
+        self.actor = actor
+        self.device = torch.device(device)
+        self.num_envs = num_envs
+        self.max_steps = max_steps
+        if proto_env is None:
+            proto_env = env_fn()
+            proto_env.reset(seed=987654321)
+        self.proto_env = proto_env
+        if spec is None:
+            # raises the engine's ValueError for configs it does not support
+            spec = compile_engine_spec(
+                proto_env, lookahead_device=self.device
+                if self.device.type == "cuda" else None)
+        self.spec = spec
+        self.gen = proto_env.cluster.jobs_generator
+        self._models_batch = build_models_batch(self.spec, self.device)
+
+    def _make_engine(self, scheds):
+        cap = max(s.n for s in scheds) + 8
+        if self.device.type == "cuda":
+            from ..cluster.gpu_engine import GpuEngine
+            eng = GpuEngine(self.spec, B=len(scheds), device=self.device,
+                            n_jobs_cap=cap)
+        else:
+            from ..cluster.vec_engine import CpuEngine
+            eng = CpuEngine(self.spec, B=len(scheds), n_jobs_cap=cap)
+        for b, sched in enumerate(scheds):
+            eng.reset_env(b, sched)
+        return eng
+
+    def _run_wave(self, seeds: List[int]) -> List[Dict]:
+        import torch
+        from ..cluster.vec_engine import drain_episode_schedule
+        t0 = time.perf_counter()
+        scheds = [drain_episode_schedule(self.gen, self.spec, seed=int(s))
+                  for s in seeds]
+        eng = self._make_engine(scheds)
+        B = len(seeds)
+        dev = eng.T["reward"].device
+        ret = torch.zeros(B, dtype=torch.float64, device=dev)
+        nsteps = torch.zeros(B, dtype=torch.int64, device=dev)
+        step = 0
+        while step < self.max_steps:
+            live = eng.T["done"] == 0
+            if not bool(live.any()):
+                break
+            actions = self.actor.act(eng, step)
+            eng.step(actions)
+            # only envs that were live before the step earned this reward
+            ret = torch.where(live, ret + eng.T["reward"], ret)
+            nsteps += live.to(torch.int64)
+            step += 1
+        ret = ret.cpu().numpy()
+        nsteps = nsteps.cpu().numpy()
+        run_time = time.perf_counter() - t0
+        out = []
+        for b, seed in enumerate(seeds):
+            es = eng.episode_stats(b)
+            n = int(nsteps[b])
+            r = {
+                "seed": int(seed),
+                "episode_stats": es,
+                "num_actor_steps": n,
+                "episode_return": float(ret[b]),
+                "mean_reward": float(ret[b] / n) if n else 0.0,
+                # the wave's wall time, shared by its envs
+                "run_time": run_time,
+            }
+            for key in ("job_completion_time", "job_completion_time_speedup"):
+                vals = es.get(key, [])
+                r[f"mean_{key}"] = float(np.mean(vals)) if len(vals) else None
+            r["blocking_rate"] = es.get("blocking_rate", None)
+            r["acceptance_rate"] = es.get("acceptance_rate", None)
+            out.append(r)
+        return out
+
+    def run(self, seeds) -> List[Dict]:
+        seeds = [int(s) for s in seeds]
+        self.actor.prepare(self)
+        width = self.num_envs or max(len(seeds), 1)
+        results: List[Dict] = []
+        for i in range(0, len(seeds), width):
+            results.extend(self._run_wave(seeds[i:i + width]))
+        return results
+
+
 class PolicyActor:
     """Greedy/stochastic actor wrapping a trained GNNPolicy for EvalLoop."""
 

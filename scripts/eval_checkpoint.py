@@ -21,6 +21,13 @@ def main():
         "configs", "train_config.yaml"))
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--stochastic", action="store_true")
+    ap.add_argument("--backend", choices=("env", "engine"), default="env",
+                    help="env: one Python env per episode (EvalLoop); "
+                         "engine: all seeds at once on the vectorised env "
+                         "engine with the device-side policy actor")
+    ap.add_argument("--seeds", type=int, default=None,
+                    help="number of consecutive eval seeds (default: "
+                         "--episodes)")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args()
 
@@ -32,8 +39,38 @@ def main():
         config=cfg.get("model", {}).get("custom_model_config"),
         deterministic=not args.stochastic)
 
+    episodes = args.episodes if args.seeds is None else args.seeds
+    fields = ("blocking_rate", "acceptance_rate", "mean_job_completion_time",
+              "mean_job_completion_time_speedup", "episode_return")
+    if args.backend == "engine":
+        import torch
+        from ddls_amd.rl.device_actor import DeviceActor
+        from ddls_amd.runtime.loops import EngineEvalLoop
+        device = torch.device("cuda:0" if torch.cuda.is_available()
+                              else "cpu")
+        seed_everything(eval_seed)
+        dev_actor = DeviceActor.policy(actor.policy.to(device),
+                                       deterministic=not args.stochastic,
+                                       seed=eval_seed)
+        # raises the engine's ValueError for a config it does not support
+        loop = EngineEvalLoop(dev_actor, lambda: build_env_from_config(cfg),
+                              device)
+        rows = []
+        for ep, r in enumerate(loop.run(range(eval_seed,
+                                              eval_seed + episodes))):
+            row = {"episode": ep, "seed": r["seed"]}
+            row.update({k: r[k] for k in fields})
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        mean = {"episode": "mean"}
+        for k in fields:
+            vals = [row[k] for row in rows if row[k] is not None]
+            mean[k] = float(sum(vals) / len(vals)) if vals else None
+        print(json.dumps(mean), flush=True)
+        return
+
     all_results = []
-    for ep in range(args.episodes):
+    for ep in range(episodes):
         seed_everything(eval_seed + ep)
         env = build_env_from_config(cfg)
         loop = EvalLoop(actor, env)

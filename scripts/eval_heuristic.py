@@ -23,13 +23,78 @@ def main():
         os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
         "configs", "heuristic_config.yaml"))
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--backend", choices=("env", "engine"), default="env",
+                    help="env: one Python env per episode (EvalLoop); "
+                         "engine: all seeds at once on the vectorised env "
+                         "engine with device-side actors (EngineEvalLoop)")
+    ap.add_argument("--seeds", type=int, default=1,
+                    help="number of consecutive seeds, starting at the "
+                         "config's seed")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args()
 
     cfg = load_config(args.config, overrides=args.overrides)
     seed = cfg.get("seed", 1799)
 
+    fields = ("blocking_rate", "acceptance_rate", "mean_job_completion_time",
+              "mean_job_completion_time_speedup", "episode_return",
+              "num_actor_steps", "run_time")
+
+    def report(actor_name, per_seed):
+        """One line per (actor, seed) and a mean line over the seeds."""
+        rows = []
+        for r in per_seed:
+            row = {k: r[k] for k in fields}
+            rows.append(row)
+            print(f"{actor_name}[{r['seed']}]: {json.dumps(row)}", flush=True)
+        mean = {}
+        for k in fields:
+            vals = [row[k] for row in rows if row[k] is not None]
+            mean[k] = float(sum(vals) / len(vals)) if vals else None
+        print(f"{actor_name}[mean]: {json.dumps(mean)}", flush=True)
+        return {"seeds": {str(r["seed"]): row
+                          for r, row in zip(per_seed, rows)}, "mean": mean}
+
+    def run_engine():
+        import torch
+        from ddls_amd.rl.device_actor import DeviceActor
+        from ddls_amd.runtime.loops import EngineEvalLoop
+        device = torch.device("cuda:0" if torch.cuda.is_available()
+                              else "cpu")
+        seed_everything(seed)
+        # raises the engine's ValueError for a config it does not support
+        loop = EngineEvalLoop(None, lambda: build_env_from_config(cfg),
+                              device)
+        results = {}
+        for actor_name in cfg.get("actors", list(ACTORS)):
+            kwargs = {"seed": seed}
+            if actor_name == "sip_ml":
+                kwargs["max_partitions_per_op"] = cfg.get("sip_ml_cap", 8)
+            loop.actor = DeviceActor.heuristic(actor_name, **kwargs)
+            results[actor_name] = report(
+                actor_name, loop.run(range(seed, seed + args.seeds)))
+        return results
+
+    def run_env_seeds():
+        results = {}
+        for actor_name in cfg.get("actors", list(ACTORS)):
+            per_seed = []
+            for s in range(seed, seed + args.seeds):
+                seed_everything(s)
+                env = build_env_from_config(cfg)
+                kwargs = ({"max_partitions_per_op": cfg.get("sip_ml_cap", 8)}
+                          if actor_name == "sip_ml" else {})
+                r = EvalLoop(ACTORS[actor_name](**kwargs), env).run(seed=s)
+                r["seed"] = s
+                per_seed.append(r)
+            results[actor_name] = report(actor_name, per_seed)
+        return results
+
     def run_all():
+        if args.backend == "engine":
+            return run_engine()
+        if args.seeds != 1:
+            return run_env_seeds()
         results = {}
         for actor_name in cfg.get("actors", list(ACTORS)):
             seed_everything(seed)
