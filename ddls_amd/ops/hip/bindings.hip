@@ -73,6 +73,21 @@ std::vector<torch::Tensor> ppo_loss_bwd(
     torch::Tensor p, torch::Tensor lp, torch::Tensor coef, torch::Tensor h,
     torch::Tensor actions, torch::Tensor values, torch::Tensor vtarg,
     torch::Tensor gl, double vf_clip, double vf_coef, double ent_coef);
+std::vector<torch::Tensor> vtrace_scan(
+    torch::Tensor rewards, torch::Tensor dones, torch::Tensor values,
+    torch::Tensor bootstrap, torch::Tensor rho, torch::Tensor c,
+    double gamma);
+std::vector<torch::Tensor> impala_loss_fwd(
+    torch::Tensor logits, torch::Tensor values, torch::Tensor actions,
+    torch::Tensor behaviour_logp, torch::Tensor rewards, torch::Tensor dones,
+    torch::Tensor bootstrap, int64_t T, int64_t N, double gamma,
+    double rho_clip, double pg_rho_clip, double c_clip, double vf_coeff,
+    double ent_coeff, bool drop_last);
+std::vector<torch::Tensor> impala_loss_bwd(
+    torch::Tensor p, torch::Tensor lp, torch::Tensor h,
+    torch::Tensor actions, torch::Tensor values, torch::Tensor vs,
+    torch::Tensor pg_adv, torch::Tensor gl, int64_t T, int64_t N,
+    double vf_coeff, double ent_coeff, bool drop_last);
 void env_step_batch(std::vector<torch::Tensor> T, std::vector<double> fscal,
                     std::vector<int64_t> iscal);
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs);
@@ -128,6 +143,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "CSR segment mean of stored message activations");
     m.def("ppo_loss_fwd", &ppo_loss_fwd, "fused PPO clipped-surrogate loss");
     m.def("ppo_loss_bwd", &ppo_loss_bwd, "analytic PPO loss backward");
+    m.def("vtrace_scan", &vtrace_scan,
+          "V-trace recurrence over [T, N], bit-equal to vtrace_targets");
+    m.def("impala_loss_fwd", &impala_loss_fwd,
+          "fused IMPALA loss: row softmax, V-trace scan, ordered reduction");
+    m.def("impala_loss_bwd", &impala_loss_bwd,
+          "analytic IMPALA loss backward");
     m.def("segment_mean_bwd", &segment_mean_bwd,
           "per-graph mean backward (broadcast/scale)");
     m.def("flat_adam", &flat_adam,

@@ -187,7 +187,9 @@ class EngineVectorEnv:
         """``device_resident=True`` keeps the per-sample training inputs as
         flat ``[T*B, ...]`` tensors on the engine's device (keys ``*_dev``)
         and returns ``obs`` as a LazyObsSeq instead of building T*B
-        CompactObs; sampling and everything GAE needs are unchanged.
+        CompactObs; sampling and everything GAE needs are unchanged.  The
+        f32 ``rewards_dev`` / ``dones_dev`` ``[T*B]`` and ``bootstrap_dev``
+        ``[B]`` serve the device IMPALA learner.
 
         ``sampler="device"`` replaces the per-step torch head + Categorical
         with one DeviceActor call in POLICY_SAMPLE mode (on a GpuEngine one
@@ -282,6 +284,10 @@ class EngineVectorEnv:
                 "actions_dev": buf_actions.reshape(n),
                 "logp_dev": buf_logp.reshape(n),
                 "lp_all_dev": buf_lp_all.reshape(n, A),
+                # what a V-trace learner needs besides the above
+                "rewards_dev": buf_rewards.reshape(n),
+                "dones_dev": buf_dones.reshape(n).float(),
+                "bootstrap_dev": bootstrap,
                 "actions": buf_actions.cpu().numpy(),
                 "lp_all": buf_lp_all.cpu().numpy(),
                 "logp": buf_logp.cpu().numpy(),

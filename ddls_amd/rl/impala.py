@@ -17,9 +17,16 @@ V-trace (Espeholt et al. 2018):
   vs_t    = V_t + delta_t + gamma c_t (vs_{t+1} - V_{t+1})
   pg_adv  = pg_rho_t (r_t + gamma vs_{t+1} - V_t)
 with rho_t = min(rho_clip, pi/mu), c_t = min(c_clip, pi/mu).
+
+Two learners (``ImpalaConfig.learner``).  ``"torch"`` stages the rollout on
+the host and evaluates the loss as a torch autograd chain.  ``"device"``
+trains from the flat device tensors of ``rollout(device_resident=True)``: the
+forward never touches ``data["obs"]``, and on a GPU the loss is the fused
+kernels of ``ops/hip/vtrace_loss.hip`` with one D2H for the stats.
 """
 from __future__ import annotations
 
+import sys
 import time
 from dataclasses import dataclass
 from typing import Dict, List, Optional
@@ -44,6 +51,13 @@ class ImpalaConfig:
     c_clip: float = 1.0
     train_batch_size: int = 4000
     vtrace_drop_last_ts: bool = True
+    # "torch": host-staged batch + autograd loss.  "device": device-resident
+    # batch + fused V-trace loss kernels (needs an env with
+    # supports_device_resident, else falls back to "torch" with a warning)
+    learner: str = "torch"
+
+
+LEARNERS = ("torch", "device")
 
 
 def vtrace_targets(rewards, dones, values, bootstrap, rho, c, gamma):
@@ -65,6 +79,80 @@ def vtrace_targets(rewards, dones, values, bootstrap, rho, c, gamma):
     return vs, pg_adv
 
 
+def impala_loss_reference(logits, values, actions, behaviour_logp, rewards,
+                          dones, bootstrap, cfg):
+    """The IMPALA loss as a torch autograd chain.  ``logits`` [T*N, A] and
+    ``values`` [T*N] carry the graph; ``actions`` [T*N]; ``rewards`` is
+    [T, N], ``behaviour_logp`` and ``dones`` are [T, N] or flat in that
+    order, ``bootstrap`` [N].  Returns (loss, dict of 0-d stat tensors)."""
+    T, N = rewards.shape
+    behaviour_logp = behaviour_logp.reshape(T, N)
+    dones = dones.reshape(T, N)
+    dist = torch.distributions.Categorical(logits=logits)
+    new_logp = dist.log_prob(actions).reshape(T, N)
+    values_tn = values.reshape(T, N)
+    with torch.no_grad():
+        log_rho = new_logp - behaviour_logp
+        rho = torch.clamp(torch.exp(log_rho), max=cfg.rho_clip)
+        pg_rho = torch.clamp(torch.exp(log_rho), max=cfg.pg_rho_clip)
+        c = torch.clamp(torch.exp(log_rho), max=cfg.c_clip)
+        vs, pg_adv_raw = vtrace_targets(rewards, dones,
+                                        values_tn.detach(), bootstrap,
+                                        rho, c, cfg.gamma)
+        pg_adv = pg_rho * pg_adv_raw
+
+    keep = slice(0, T - 1) if (cfg.vtrace_drop_last_ts and T > 1) \
+        else slice(0, T)
+    policy_loss = -(pg_adv[keep] * new_logp[keep]).mean()
+    vf_loss = 0.5 * ((vs[keep].detach() - values_tn[keep]) ** 2).mean()
+    entropy = dist.entropy().reshape(T, N)[keep].mean()
+    loss = (policy_loss + cfg.vf_loss_coeff * vf_loss
+            - cfg.entropy_coeff * entropy)
+    return loss, {"policy_loss": policy_loss.detach(),
+                  "vf_loss": vf_loss.detach(),
+                  "entropy": entropy.detach(),
+                  "total_loss": loss.detach(),
+                  "mean_rho": rho.mean()}
+
+
+STAT_KEYS = ("policy_loss", "vf_loss", "entropy", "total_loss", "mean_rho")
+
+
+class _ImpalaLossFn(torch.autograd.Function):
+    """Fused IMPALA loss (ops/hip/vtrace_loss.hip): three launches forward
+    (row softmax, V-trace scan, ordered reduction), one analytic backward.
+    Returns (loss, stats[5] in STAT_KEYS order)."""
+
+    @staticmethod
+    def forward(ctx, logits, values, actions, behaviour_logp, rewards, dones,
+                bootstrap, T, N, gamma, rho_clip, pg_rho_clip, c_clip,
+                vf_coeff, ent_coeff, drop_last):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        values = values.contiguous()
+        loss, stats, p, lp, h, vs, pg_adv = ext.impala_loss_fwd(
+            logits.contiguous(), values, actions, behaviour_logp, rewards,
+            dones, bootstrap, int(T), int(N), float(gamma), float(rho_clip),
+            float(pg_rho_clip), float(c_clip), float(vf_coeff),
+            float(ent_coeff), bool(drop_last))
+        ctx.save_for_backward(p, lp, h, actions, values, vs, pg_adv)
+        ctx.consts = (int(T), int(N), float(vf_coeff), float(ent_coeff),
+                      bool(drop_last))
+        ctx.mark_non_differentiable(stats)
+        return loss.reshape(()), stats
+
+    @staticmethod
+    def backward(ctx, gl, _gstats):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        p, lp, h, actions, values, vs, pg_adv = ctx.saved_tensors
+        T, N, vf_coeff, ent_coeff, drop_last = ctx.consts
+        glogits, gvalues = ext.impala_loss_bwd(
+            p, lp, h, actions, values, vs, pg_adv,
+            gl.reshape(1).contiguous(), T, N, vf_coeff, ent_coeff, drop_last)
+        return (glogits, gvalues) + (None,) * 14
+
+
 class ImpalaTrainer:
     """Same trainer-facing interface as PPOTrainer (train/state_dict/...)."""
 
@@ -72,6 +160,10 @@ class ImpalaTrainer:
                  device: Optional[torch.device] = None):
         self.env = vector_env
         self.config = config or ImpalaConfig()
+        if self.config.learner not in LEARNERS:
+            raise ValueError("ImpalaConfig.learner must be 'torch' or "
+                             f"'device', not {self.config.learner!r}")
+        self._learner_warned = False
         self.device = device or torch.device(
             "cuda" if torch.cuda.is_available() else "cpu")
         self.policy = policy.to(self.device)
@@ -92,12 +184,30 @@ class ImpalaTrainer:
         return (actions.cpu().numpy(), dist.log_prob(actions).cpu().numpy(),
                 values.cpu().numpy())
 
+    def _device_learner(self) -> bool:
+        """Whether this trainer trains from a device-resident rollout.  Read
+        with getattr: subclasses hold configs without the switch."""
+        if getattr(self.config, "learner", "torch") != "device":
+            return False
+        if getattr(self.env, "supports_device_resident", False):
+            return True
+        if not self._learner_warned:
+            self._learner_warned = True
+            print("[impala] learner='device' needs an env whose rollout() "
+                  "takes device_resident=True; using the torch learner",
+                  file=sys.stderr)
+        return False
+
     def collect_rollout(self, num_steps: Optional[int] = None) -> Dict:
         n_envs = len(self.env)
         steps = num_steps if num_steps is not None else max(
             1, self.config.train_batch_size // n_envs)
         if hasattr(self.env, "rollout"):
-            data = self.env.rollout(self.policy, steps)
+            if self._device_learner():
+                data = self.env.rollout(self.policy, steps,
+                                        device_resident=True)
+            else:
+                data = self.env.rollout(self.policy, steps)
             self.total_env_steps += steps * n_envs
             return data
         obs_buf, act_buf, logp_buf, val_buf, rew_buf, done_buf = \
@@ -150,10 +260,46 @@ class ImpalaTrainer:
         return self.policy.forward_flat(
             inputs["batch"], inputs["graph_features"], inputs["action_mask"])
 
-    def update(self, data: Dict) -> Dict[str, float]:
+    def _forward_device(self, data: Dict):
+        """Differentiable forward from the flat device tensors of a
+        device-resident rollout; never indexes ``data["obs"]``."""
+        from ..models.gnn import graph_mean
+        mb_static = self.env._models_batch
+        node_emb = self.policy.gnn(mb_static)
+        model_emb = graph_mean(node_emb, mb_static)
+        gfull = data["gfull_dev"]
+        graph_emb = self.policy.graph_module(gfull)
+        final = torch.cat([model_emb[data["model_ids_dev"]], graph_emb],
+                          dim=-1)
+        logits = self.policy.policy_branch(final)
+        values = self.policy.value_branch(final).squeeze(-1)
+        if self.policy.config["apply_action_mask"]:
+            logits = logits + torch.clamp(
+                torch.log(gfull[:, 17:]), min=torch.finfo(torch.float32).min)
+        return logits, values
+
+    def _loss_device(self, data: Dict):
+        """(loss, stats[5] tensor in STAT_KEYS order) of a device-resident
+        rollout: the fused kernels on a GPU, the torch chain on CPU tensors
+        (the CpuEngine backend)."""
+        cfg = self.config
+        T, N = data["rewards"].shape
+        logits, values = self._forward_device(data)
+        args = (logits, values, data["actions_dev"], data["logp_dev"])
+        if logits.is_cuda:
+            return _ImpalaLossFn.apply(
+                *args, data["rewards_dev"], data["dones_dev"],
+                data["bootstrap_dev"], T, N, cfg.gamma, cfg.rho_clip,
+                cfg.pg_rho_clip, cfg.c_clip, cfg.vf_loss_coeff,
+                cfg.entropy_coeff, cfg.vtrace_drop_last_ts)
+        loss, st = impala_loss_reference(
+            *args, data["rewards_dev"].reshape(T, N), data["dones_dev"],
+            data["bootstrap_dev"], cfg)
+        return loss, torch.stack([st[k] for k in STAT_KEYS])
+
+    def _loss_host(self, data: Dict):
         cfg = self.config
         dev = self.device
-        T, N = data["rewards"].shape
         t64 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32),
                                         device=dev)
         rewards = t64(data["rewards"])
@@ -161,29 +307,18 @@ class ImpalaTrainer:
         behavior_logp = t64(data["logp"])
         actions = torch.as_tensor(np.asarray(data["actions"]).reshape(-1),
                                   device=dev)
-
+        bootstrap = t64(data["bootstrap_values"])
         logits, values = self._forward_batch(data["obs"])   # [T*N, A], [T*N]
-        dist = torch.distributions.Categorical(logits=logits)
-        new_logp = dist.log_prob(actions).reshape(T, N)
-        values_tn = values.reshape(T, N)
-        with torch.no_grad():
-            log_rho = new_logp - behavior_logp
-            rho = torch.clamp(torch.exp(log_rho), max=cfg.rho_clip)
-            pg_rho = torch.clamp(torch.exp(log_rho), max=cfg.pg_rho_clip)
-            c = torch.clamp(torch.exp(log_rho), max=cfg.c_clip)
-            bootstrap = t64(data["bootstrap_values"])
-            vs, pg_adv_raw = vtrace_targets(rewards, dones,
-                                            values_tn.detach(), bootstrap,
-                                            rho, c, cfg.gamma)
-            pg_adv = pg_rho * pg_adv_raw
+        return impala_loss_reference(logits, values, actions, behavior_logp,
+                                     rewards, dones, bootstrap, cfg)
 
-        keep = slice(0, T - 1) if (cfg.vtrace_drop_last_ts and T > 1) \
-            else slice(0, T)
-        policy_loss = -(pg_adv[keep] * new_logp[keep]).mean()
-        vf_loss = 0.5 * ((vs[keep].detach() - values_tn[keep]) ** 2).mean()
-        entropy = dist.entropy().reshape(T, N)[keep].mean()
-        loss = (policy_loss + cfg.vf_loss_coeff * vf_loss
-                - cfg.entropy_coeff * entropy)
+    def update(self, data: Dict) -> Dict[str, float]:
+        cfg = self.config
+        on_device = self._device_learner() and "gfull_dev" in data
+        if on_device:
+            loss, stats_t = self._loss_device(data)
+        else:
+            loss, stats_d = self._loss_host(data)
 
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
@@ -192,13 +327,13 @@ class ImpalaTrainer:
             torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
                                            cfg.grad_clip)
         self.optimizer.step()
-        return {
-            "policy_loss": float(policy_loss.item()),
-            "vf_loss": float(vf_loss.item()),
-            "entropy": float(entropy.item()),
-            "total_loss": float(loss.item()),
-            "mean_rho": float(rho.mean().item()),
-        }
+        if on_device:
+            # one D2H for all five stats
+            stats = dict(zip(STAT_KEYS, stats_t.detach().tolist()))
+        else:
+            stats = {k: float(stats_d[k].item()) for k in STAT_KEYS}
+        stats["learner"] = 1 if on_device else 0
+        return stats
 
     # ------------------------------------------------------------------
     def train(self, num_steps: Optional[int] = None) -> Dict[str, float]:

@@ -228,7 +228,8 @@ def build_trainer_from_config(cfg: dict, device=None):
             pg_rho_clip=algo.get("vtrace_clip_pg_rho_threshold", 1.0),
             c_clip=algo.get("vtrace_clip_c_threshold", 1.0),
             train_batch_size=algo.get("train_batch_size", 4000),
-            vtrace_drop_last_ts=algo.get("vtrace_drop_last_ts", True))
+            vtrace_drop_last_ts=algo.get("vtrace_drop_last_ts", True),
+            learner=str(algo.get("learner", "torch")))
         return ImpalaTrainer(venv, policy, imp_cfg, device=device)
     ppo_cfg = PPOConfig(
         lr=algo.get("lr", 2.785e-4),

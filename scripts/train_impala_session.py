@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """IMPALA (V-trace) / PG training session on the GPU-resident env engine —
 demonstrates the non-PPO algorithms end-to-end on the flagship stack.
-Env: ALGO=impala|pg ITERS=N OUT=dir"""
+Env: ALGO=impala|pg ITERS=N OUT=dir LEARNER=torch|device (IMPALA only);
+EVAL=0 skips the greedy evaluation after training."""
 import json
 import os
 import sys
@@ -19,6 +20,7 @@ from ddls_amd.rl.pg import PGConfig, PGTrainer
 ALGO = os.environ.get("ALGO", "impala")
 ITERS = int(os.environ.get("ITERS", "40"))
 OUT = os.environ.get("OUT", f"gpurun_out/{ALGO}_session")
+LEARNER = os.environ.get("LEARNER", "torch")
 
 
 def main():
@@ -32,15 +34,18 @@ def main():
         tr = PGTrainer(venv, policy, PGConfig(train_batch_size=4096),
                        device=dev)
     else:
-        tr = ImpalaTrainer(venv, policy, ImpalaConfig(train_batch_size=4096),
-                           device=dev)
+        tr = ImpalaTrainer(venv, policy,
+                           ImpalaConfig(train_batch_size=4096,
+                                        learner=LEARNER), device=dev)
     log = []
     t0 = time.time()
     for i in range(ITERS):
         st = tr.train(num_steps=16)
         log.append({k: st.get(k) for k in ("iteration", "mean_reward",
                                            "total_loss", "mean_rho",
-                                           "entropy")})
+                                           "entropy", "learner",
+                                           "rollout_time_s",
+                                           "update_time_s")})
         if (i + 1) % 10 == 0:
             print(f"iter {i+1}: reward {st['mean_reward']:.1f} "
                   f"loss {st['total_loss']:.1f} "
@@ -49,9 +54,19 @@ def main():
     dt = time.time() - t0
     print(f"{ALGO}: {tr.total_env_steps} env steps in {dt:.0f}s = "
           f"{tr.total_env_steps/dt:,.0f} steps/s")
+    # how an iteration divides (the first one carries warm-up, leave it out)
+    tail = log[1:] or log
+    print(json.dumps({
+        "algo": ALGO, "learner": LEARNER, "iters": ITERS,
+        "env_steps_per_s": tr.total_env_steps / dt,
+        "rollout_ms": 1e3 * sum(r["rollout_time_s"] for r in tail) / len(tail),
+        "update_ms": 1e3 * sum(r["update_time_s"] for r in tail) / len(tail),
+        "final_mean_reward": log[-1]["mean_reward"]}), flush=True)
     with open(f"{OUT}/train_log.json", "w") as f:
         json.dump(log, f)
     torch.save({"policy": policy.state_dict()}, f"{OUT}/policy.pt")
+    if os.environ.get("EVAL", "1") == "0":
+        return
 
     # greedy full-episode eval on the REAL env vs the two strongest
     # heuristics, same protocol as scripts/train_eval_session.py
