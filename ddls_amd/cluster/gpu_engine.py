@@ -159,7 +159,7 @@ class GpuEngine:
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         self.SCH = sch_cap
         self.NJOBS = njobs_cap
-        self.T.update({
+        state = {
             "sch_model": z((B, sch_cap), torch.int32),
             "sch_frac": z((B, sch_cap), torch.float64),
             "sch_acc": z((B, sch_cap), torch.float64),
@@ -199,7 +199,10 @@ class GpuEngine:
             "tp_info": z((B,), torch.float64),
             "tp_time": z((B,), torch.float64),
             "actions": z((B,), torch.int32),
-        })
+        }
+        self.T.update(state)
+        # every per-env tensor (leading dim B): what replicate_envs copies
+        self._env_keys = tuple(state)
         self._state_alloc_done = True
 
     # ------------------------------------------------------------------
@@ -251,6 +254,36 @@ class GpuEngine:
         T["obs_mask"][b] = torch.as_tensor(mask, device=dev)
         T["obs_model"][b] = mid
         T["obs_sched"][b] = 0
+
+    def replicate_envs(self, src_rows, dst_rows):
+        """Make env ``dst_rows[i]`` a copy of env ``src_rows[i]``: the row of
+        every per-env tensor (device-side indexed copies, no host round trip)
+        and the ``schedules[]`` entry.  ``dst_rows`` must not repeat and must
+        not overlap ``src_rows``."""
+        src_rows = [int(b) for b in src_rows]
+        dst_rows = [int(b) for b in dst_rows]
+        if len(src_rows) != len(dst_rows):
+            raise ValueError("replicate_envs: src_rows and dst_rows differ in "
+                             "length")
+        if not dst_rows:
+            return
+        if not self._state_alloc_done:
+            raise RuntimeError("replicate_envs: no env has been reset yet")
+        if len(set(dst_rows)) != len(dst_rows) or \
+                set(dst_rows) & set(src_rows):
+            raise ValueError("replicate_envs: dst_rows must be distinct and "
+                             "disjoint from src_rows")
+        for b in src_rows + dst_rows:
+            if not 0 <= b < self.B:
+                raise IndexError(f"replicate_envs: env {b} outside "
+                                 f"[0, {self.B})")
+        src = torch.as_tensor(src_rows, dtype=torch.int64, device=self.device)
+        dst = torch.as_tensor(dst_rows, dtype=torch.int64, device=self.device)
+        for k in self._env_keys:
+            t = self.T[k]
+            t.index_copy_(0, dst, t.index_select(0, src))
+        for s, d in zip(src_rows, dst_rows):
+            self.schedules[d] = self.schedules[s]
 
     # ------------------------------------------------------------------
     _ORDER = ("static_ok", "shape_ptr", "shapes", "model_gf", "model_seq",

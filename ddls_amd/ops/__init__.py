@@ -30,6 +30,7 @@ _SOURCES = [os.path.join(_HERE, "hip", "meanpool.hip"),
             os.path.join(_HERE, "hip", "cached_step.hip"),
             os.path.join(_HERE, "hip", "batch_stage.hip"),
             os.path.join(_HERE, "hip", "actor.hip"),
+            os.path.join(_HERE, "hip", "es_population.hip"),
             os.path.join(_HERE, "hip", "bindings.hip")]
 # headers the sources include: not compiled on their own, but a built library
 # older than one of them is stale

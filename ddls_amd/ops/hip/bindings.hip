@@ -122,6 +122,17 @@ void actor_batch(torch::Tensor obs_gf, torch::Tensor obs_mask,
                  uint64_t seed, uint64_t step, torch::Tensor actions,
                  torch::Tensor gfull, torch::Tensor lp_all,
                  torch::Tensor logp, torch::Tensor value, torch::Tensor u);
+void es_perturb(torch::Tensor theta, double sigma, uint64_t seed,
+                uint64_t generation, torch::Tensor eps, torch::Tensor pop);
+void es_update(torch::Tensor theta, torch::Tensor eps, torch::Tensor w,
+               double scale, double decay, torch::Tensor out);
+void actor_population(torch::Tensor obs_gf, torch::Tensor obs_mask,
+                      torch::Tensor obs_model, torch::Tensor done,
+                      torch::Tensor pop, torch::Tensor model_emb_pop,
+                      std::vector<int64_t> head_offs, int64_t E, int64_t mode,
+                      uint64_t seed, uint64_t step, torch::Tensor actions,
+                      torch::Tensor lp_all, torch::Tensor logp,
+                      torch::Tensor value, torch::Tensor u);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("row_mlp", &row_mlp, "fused LN+Linear+ReLU over rows");
@@ -193,4 +204,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("actor_batch", &actor_batch,
           "device-side actors over vectorised envs: GNN policy head (greedy "
           "or Philox-sampled) and the six heuristic baselines, one launch");
+    m.def("es_perturb", &es_perturb,
+          "ES: Philox/Box-Muller noise eps [K,n] and the antithetic "
+          "population pop [2K,n] = theta +- sigma * eps, one launch");
+    m.def("es_update", &es_update,
+          "ES: theta' = (theta + scale * sum_k w[k] eps[k]) - decay * theta");
+    m.def("actor_population", &actor_population,
+          "actor_batch's policy modes with the head weights and embedding "
+          "table of row b taken from population member b / E, one launch");
 }

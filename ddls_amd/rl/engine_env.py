@@ -85,6 +85,9 @@ class EngineVectorEnv:
     supports_device_resident = True
     # rollout() takes sampler="device" (one actor_batch launch per step)
     supports_device_sampler = True
+    # rl.es_population.PopulationEvaluator may borrow spec / gen / models
+    # batch / device / base_seed for an engine of its own
+    supports_population_eval = True
 
     def __init__(self, env_fn, num_envs: int, device, base_seed: int = 0,
                  spec=None, proto_env=None, verbose: bool = False):

@@ -192,7 +192,12 @@ def build_trainer_from_config(cfg: dict, device=None):
             stepsize=algo.get("stepsize", 0.01),
             l2_coeff=algo.get("l2_coeff", 0.005),
             perturbation_pairs=algo.get("perturbation_pairs", 16),
-            fragment_steps=algo.get("fragment_steps", 16))
+            fragment_steps=algo.get("fragment_steps", 16),
+            evaluator=algo.get("evaluator", "sequential"),
+            envs_per_member=algo.get("envs_per_member", 8),
+            eval_max_steps=algo.get("eval_max_steps", 100000),
+            noise_seed=algo.get("noise_seed", 0),
+            deterministic_eval=algo.get("deterministic_eval", False))
         return ESTrainer(venv, policy, es_cfg, device=device)
     if algo.get("name", "ppo") == "dqn":
         from ..rl.dqn import DQNConfig, DQNTrainer
