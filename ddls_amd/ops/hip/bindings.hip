@@ -88,6 +88,20 @@ std::vector<torch::Tensor> impala_loss_bwd(
     torch::Tensor actions, torch::Tensor values, torch::Tensor vs,
     torch::Tensor pg_adv, torch::Tensor gl, int64_t T, int64_t N,
     double vf_coeff, double ent_coeff, bool drop_last);
+int64_t dqn_nstep_ingest(
+    torch::Tensor gfull, torch::Tensor model_ids, torch::Tensor actions,
+    torch::Tensor rewards, torch::Tensor dones,
+    std::vector<torch::Tensor> ring, int64_t T, int64_t N, int64_t capacity,
+    int64_t written, int64_t n_step, double gamma);
+std::vector<torch::Tensor> dqn_loss_fwd(
+    torch::Tensor logits_s, torch::Tensor values_s, torch::Tensor logits_no,
+    torch::Tensor values_no, torch::Tensor logits_nt, torch::Tensor values_nt,
+    torch::Tensor actions, torch::Tensor ret, torch::Tensor disc,
+    torch::Tensor has_next, double v_min, double v_max, bool dueling,
+    bool double_q);
+std::vector<torch::Tensor> dqn_loss_bwd(
+    torch::Tensor logits_s, torch::Tensor actions, torch::Tensor dq,
+    torch::Tensor gl, bool dueling);
 void env_step_batch(std::vector<torch::Tensor> T, std::vector<double> fscal,
                     std::vector<int64_t> iscal);
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs);
@@ -160,6 +174,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused IMPALA loss: row softmax, V-trace scan, ordered reduction");
     m.def("impala_loss_bwd", &impala_loss_bwd,
           "analytic IMPALA loss backward");
+    m.def("dqn_nstep_ingest", &dqn_nstep_ingest,
+          "n-step transitions of a [T, N] fragment written into the replay "
+          "ring, bit-equal to nstep_transitions_reference");
+    m.def("dqn_loss_fwd", &dqn_loss_fwd,
+          "fused dueling double-DQN TD loss: row kernel, ordered reduction");
+    m.def("dqn_loss_bwd", &dqn_loss_bwd, "analytic DQN loss backward");
     m.def("segment_mean_bwd", &segment_mean_bwd,
           "per-graph mean backward (broadcast/scale)");
     m.def("flat_adam", &flat_adam,

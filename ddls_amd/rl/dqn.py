@@ -16,6 +16,14 @@ Mapping onto this stack:
 - Unlike the reference (which DISABLES action masking for DQN as a
   workaround for an RLlib crash, apex_dqn.yaml "TEMP HACK"), masking works
   here: invalid actions carry -inf Q and are never selected.
+
+Two learners (``DQNConfig.learner``).  ``"torch"`` keeps the replay buffer as
+a Python list of transitions and evaluates the loss as a torch autograd
+chain.  ``"device"`` trains from the flat device tensors of
+``rollout(device_resident=True)``: the n-step transitions go straight into a
+``DeviceReplay`` ring, the forward is head-only and never touches
+``data["obs"]``, and on a GPU the loss is the fused kernels of
+``ops/hip/dqn_loss.hip`` with one D2H per update for the stats.
 """
 from __future__ import annotations
 
@@ -27,7 +35,8 @@ import torch
 import torch.nn.functional as F
 
 from ..parallel import all_reduce_gradients
-from .impala import ImpalaTrainer
+from .device_replay import DeviceReplay
+from .impala import LEARNERS, ImpalaTrainer
 from .rollout import CompactObs
 
 
@@ -48,6 +57,116 @@ class DQNConfig:
     replay_capacity: int = 200_000
     learning_starts: int = 2_000
     grad_clip: Optional[float] = 40.0
+    # "torch": host list replay + autograd loss.  "device": device replay
+    # ring + fused TD-loss kernels (needs an env with
+    # supports_device_resident, else falls back to "torch" with a warning)
+    learner: str = "torch"
+
+
+def nstep_transitions_reference(rewards, dones, n_step: int, gamma: float):
+    """The n-step numerics of ``DQNTrainer._ingest`` on f32 rewards, written
+    with explicit casts: the return ``R`` is accumulated in f32, the running
+    discount is an f64 rounded to f32 for each multiply, and ``disc`` is that
+    f64 rounded to f32 once.  The return stops at the first done.
+
+    ``rewards`` / ``dones`` are [T, N].  Returns, each [max(T - n_step, 0),
+    N]: ``ret`` f32, ``disc`` f32 (gamma ** steps), ``has_next`` bool (False
+    where a done cut the return) and ``steps`` int64 (rewards accumulated,
+    so the next state of transition (t, b) is row ``(t + steps) * N + b``)."""
+    r = np.asarray(rewards, dtype=np.float32)
+    d = np.asarray(dones) != 0
+    T, N = r.shape
+    M = max(T - int(n_step), 0)
+    ret = np.zeros((M, N), dtype=np.float32)
+    disc = np.ones((M, N), dtype=np.float64)
+    steps = np.zeros((M, N), dtype=np.int64)
+    alive = np.ones((M, N), dtype=bool)
+    discount = np.float64(1.0)
+    if M > 0:
+        for i in range(int(n_step)):
+            term = np.float32(discount) * r[i:i + M]
+            ret = np.where(alive, ret + term, ret).astype(np.float32)
+            discount = np.float64(discount * np.float64(gamma))
+            disc = np.where(alive, discount, disc)
+            steps = steps + alive
+            alive = alive & ~d[i:i + M]
+    return ret, disc.astype(np.float32), alive, steps
+
+
+def dueling_q(logits, values, dueling: bool):
+    """Q(s, .) from the policy head's outputs, as ``DQNTrainer._q_values``
+    recombines them: masked actions (logit at f32-min) are left out of the
+    advantage mean and keep their raw logit."""
+    if not dueling:
+        return logits
+    valid = logits > -1e30
+    adv = torch.where(valid, logits, torch.zeros_like(logits))
+    mean_adv = adv.sum(-1) / valid.sum(-1).clamp(min=1)
+    q = values.unsqueeze(-1) + logits - mean_adv.unsqueeze(-1)
+    return torch.where(valid, q, logits)
+
+
+STAT_KEYS = ("total_loss", "q_mean", "td_abs_mean", "target_mean")
+
+
+def dqn_loss_reference(logits_s, values_s, logits_no, values_no, logits_nt,
+                       values_nt, actions, ret, disc, has_next, v_min, v_max,
+                       dueling: bool, double_q: bool):
+    """The loss of ``DQNTrainer.update()`` as a torch autograd chain over
+    whole-minibatch tensors.  ``logits_s`` [B, A] / ``values_s`` [B] are the
+    online net on s and carry the graph; ``*_no`` / ``*_nt`` are the online
+    and the target net on s' and are constants; ``has_next`` [B] is 0 where
+    the n-step return was cut, and such a row bootstraps from 0 whatever its
+    s' rows hold.  Returns (loss, dict of 0-d stat tensors in STAT_KEYS)."""
+    with torch.no_grad():
+        q_next_t = dueling_q(logits_nt, values_nt, dueling)
+        if double_q:
+            a_star = dueling_q(logits_no, values_no, dueling).argmax(-1)
+            vals = q_next_t.gather(1, a_star.unsqueeze(1)).squeeze(1)
+        else:
+            vals = q_next_t.max(-1).values
+        boot = torch.where(has_next > 0, vals, torch.zeros_like(vals))
+        target = torch.clamp(ret + disc * boot, v_min, v_max)
+    q = dueling_q(logits_s, values_s, dueling)
+    q_a = q.gather(1, actions.unsqueeze(1)).squeeze(1)
+    loss = F.smooth_l1_loss(q_a, target)
+    return loss, {"total_loss": loss.detach(),
+                  "q_mean": q_a.detach().mean(),
+                  "td_abs_mean": (q_a.detach() - target).abs().mean(),
+                  "target_mean": target.mean()}
+
+
+class _DQNLossFn(torch.autograd.Function):
+    """Fused DQN TD loss (ops/hip/dqn_loss.hip): two launches forward (row
+    kernel, ordered reduction), one analytic backward.  Only ``logits_s`` and
+    ``values_s`` take a gradient.  Returns (loss, stats[4] in STAT_KEYS
+    order)."""
+
+    @staticmethod
+    def forward(ctx, logits_s, values_s, logits_no, values_no, logits_nt,
+                values_nt, actions, ret, disc, has_next, v_min, v_max,
+                dueling, double_q):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        logits_s = logits_s.contiguous()
+        loss, stats, dq = ext.dqn_loss_fwd(
+            logits_s, values_s.contiguous(), logits_no.contiguous(),
+            values_no.contiguous(), logits_nt.contiguous(),
+            values_nt.contiguous(), actions, ret, disc, has_next,
+            float(v_min), float(v_max), bool(dueling), bool(double_q))
+        ctx.save_for_backward(logits_s, actions, dq)
+        ctx.dueling = bool(dueling)
+        ctx.mark_non_differentiable(stats)
+        return loss.reshape(()), stats
+
+    @staticmethod
+    def backward(ctx, gl, _gstats):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        logits_s, actions, dq = ctx.saved_tensors
+        glogits, gvalues = ext.dqn_loss_bwd(
+            logits_s, actions, dq, gl.reshape(1).contiguous(), ctx.dueling)
+        return (glogits, gvalues) + (None,) * 12
 
 
 class DQNTrainer(ImpalaTrainer):
@@ -56,6 +175,9 @@ class DQNTrainer(ImpalaTrainer):
     def __init__(self, vector_env, policy, config: Optional[DQNConfig] = None,
                  device: Optional[torch.device] = None):
         cfg = config or DQNConfig()
+        if cfg.learner not in LEARNERS:
+            raise ValueError("DQNConfig.learner must be 'torch' or "
+                             f"'device', not {cfg.learner!r}")
         super().__init__(vector_env, policy, None, device=device)
         self.config = cfg
         self.optimizer = torch.optim.Adam(self.policy.parameters(),
@@ -67,6 +189,8 @@ class DQNTrainer(ImpalaTrainer):
         # list-based ring buffer (deque indexing is O(n))
         self.replay: List = []
         self._replay_ptr = 0
+        # the device learner's ring, made on the first device-resident batch
+        self.replay_dev: Optional[DeviceReplay] = None
 
     # Q(s, .) with the dueling recombination over masked actions
     def _q_values(self, obs: List[CompactObs], net):
@@ -120,11 +244,99 @@ class DQNTrainer(ImpalaTrainer):
                     self._replay_ptr = (self._replay_ptr + 1) \
                         % cfg.replay_capacity
 
+    # ------------------------------------------------------------------
+    def _heads(self, net, model_emb, gfull, model_ids):
+        """(logits, values) of ``net``'s heads over flat state rows, given
+        ``net``'s per-model GNN embeddings (ImpalaTrainer._forward_device)."""
+        graph_emb = net.graph_module(gfull)
+        final = torch.cat([model_emb[model_ids], graph_emb], dim=-1)
+        logits = net.policy_branch(final)
+        values = net.value_branch(final).squeeze(-1)
+        if net.config["apply_action_mask"]:
+            logits = logits + torch.clamp(
+                torch.log(gfull[:, 17:]), min=torch.finfo(torch.float32).min)
+        return logits, values
+
+    def _loss_device(self, mb: Dict, target_emb):
+        """(loss, stats[4] tensor in STAT_KEYS order) of one ring minibatch:
+        the fused kernels on a GPU, the torch chain on CPU tensors (the
+        CpuEngine backend)."""
+        from ..models.gnn import graph_mean
+        cfg = self.config
+        mb_static = self.env._models_batch
+        model_emb = graph_mean(self.policy.gnn(mb_static), mb_static)
+        logits_s, values_s = self._heads(self.policy, model_emb,
+                                         mb["s_gfull"], mb["s_model"])
+        with torch.no_grad():
+            # same weights as the pass above, so its embeddings serve s'
+            logits_no, values_no = self._heads(
+                self.policy, model_emb.detach(), mb["n_gfull"], mb["n_model"])
+            logits_nt, values_nt = self._heads(
+                self.target, target_emb, mb["n_gfull"], mb["n_model"])
+        args = (logits_s, values_s, logits_no, values_no, logits_nt,
+                values_nt, mb["action"], mb["ret"], mb["disc"],
+                mb["has_next"], cfg.v_min, cfg.v_max, cfg.dueling,
+                cfg.double_q)
+        if logits_s.is_cuda:
+            return _DQNLossFn.apply(*args)
+        loss, st = dqn_loss_reference(*args)
+        return loss, torch.stack([st[k] for k in STAT_KEYS])
+
+    def _update_device(self, data: Dict) -> Dict[str, float]:
+        from ..models.gnn import graph_mean
+        cfg = self.config
+        if self.replay_dev is None:
+            self.replay_dev = DeviceReplay(cfg.replay_capacity,
+                                           data["gfull_dev"].shape[1],
+                                           data["gfull_dev"].device)
+        replay = self.replay_dev
+        replay.ingest(data, cfg.n_step, cfg.gamma)
+        stats = {k: 0.0 for k in STAT_KEYS}
+        if len(replay) >= cfg.learning_starts and cfg.num_sgd_iter > 0:
+            rng = np.random.RandomState(self.iteration)
+            # the torch learner's draws, uploaded once
+            idx = torch.as_tensor(
+                np.stack([rng.randint(0, len(replay),
+                                      size=cfg.sgd_minibatch_size)
+                          for _ in range(cfg.num_sgd_iter)]),
+                device=replay.device)
+            with torch.no_grad():
+                mb_static = self.env._models_batch
+                target_emb = graph_mean(self.target.gnn(mb_static), mb_static)
+            acc = torch.zeros(len(STAT_KEYS), device=replay.device)
+            for k in range(cfg.num_sgd_iter):
+                loss, stats_t = self._loss_device(replay.gather(idx[k]),
+                                                  target_emb)
+                self.optimizer.zero_grad(set_to_none=True)
+                loss.backward()
+                all_reduce_gradients(self.policy.parameters())
+                if cfg.grad_clip is not None:
+                    torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
+                                                   cfg.grad_clip)
+                self.optimizer.step()
+                acc += stats_t.detach()
+            # one D2H for all stats of all minibatches
+            stats = dict(zip(STAT_KEYS, (acc / cfg.num_sgd_iter).tolist()))
+        stats["replay"] = len(replay)
+        stats["learner"] = 1
+        self._sync_target(data)
+        return stats
+
+    def _sync_target(self, data: Dict):
+        # target sync on an env-step cadence (reference: 100k tuned)
+        self._steps_since_sync += int(np.prod(data["rewards"].shape))
+        if self._steps_since_sync >= self.config.target_network_update_freq:
+            self.target.load_state_dict(self.policy.state_dict())
+            self._steps_since_sync = 0
+
     def update(self, data: Dict) -> Dict[str, float]:
         cfg = self.config
+        if self._device_learner() and "gfull_dev" in data:
+            return self._update_device(data)
         self._ingest(data)
         if len(self.replay) < cfg.learning_starts:
-            return {"total_loss": 0.0, "q_mean": 0.0, "replay": len(self.replay)}
+            return {"total_loss": 0.0, "q_mean": 0.0,
+                    "replay": len(self.replay), "learner": 0}
         rng = np.random.RandomState(self.iteration)
         stats = {"total_loss": 0.0, "q_mean": 0.0}
         n_updates = 0
@@ -170,11 +382,8 @@ class DQNTrainer(ImpalaTrainer):
         for k in ("total_loss", "q_mean"):
             stats[k] /= max(n_updates, 1)
         stats["replay"] = len(self.replay)
-        # target sync on an env-step cadence (reference: 100k tuned)
-        self._steps_since_sync += int(np.prod(data["rewards"].shape))
-        if self._steps_since_sync >= cfg.target_network_update_freq:
-            self.target.load_state_dict(self.policy.state_dict())
-            self._steps_since_sync = 0
+        stats["learner"] = 0
+        self._sync_target(data)
         return stats
 
     # ------------------------------------------------------------------

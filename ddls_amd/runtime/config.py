@@ -212,7 +212,8 @@ def build_trainer_from_config(cfg: dict, device=None):
             v_max=algo.get("v_max", 1000.0),
             train_batch_size=algo.get("train_batch_size", 4096),
             sgd_minibatch_size=algo.get("sgd_minibatch_size", 256),
-            num_sgd_iter=algo.get("num_sgd_iter", 4))
+            num_sgd_iter=algo.get("num_sgd_iter", 4),
+            learner=str(algo.get("learner", "torch")))
         return DQNTrainer(venv, policy, dq, device=device)
     if algo.get("name", "ppo") == "pg":
         from ..rl.pg import PGConfig, PGTrainer
