@@ -25,6 +25,7 @@ _SOURCES = [os.path.join(_HERE, "hip", "meanpool.hip"),
             os.path.join(_HERE, "hip", "ppo_loss.hip"),
             os.path.join(_HERE, "hip", "vtrace_loss.hip"),
             os.path.join(_HERE, "hip", "dqn_loss.hip"),
+            os.path.join(_HERE, "hip", "per_replay.hip"),
             os.path.join(_HERE, "hip", "policy_head.hip"),
             os.path.join(_HERE, "hip", "lookahead.hip"),
             os.path.join(_HERE, "hip", "env_step.hip"),

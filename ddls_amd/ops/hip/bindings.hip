@@ -99,9 +99,25 @@ std::vector<torch::Tensor> dqn_loss_fwd(
     torch::Tensor actions, torch::Tensor ret, torch::Tensor disc,
     torch::Tensor has_next, double v_min, double v_max, bool dueling,
     bool double_q);
+std::vector<torch::Tensor> dqn_loss_fwd_weighted(
+    torch::Tensor logits_s, torch::Tensor values_s, torch::Tensor logits_no,
+    torch::Tensor values_no, torch::Tensor logits_nt, torch::Tensor values_nt,
+    torch::Tensor actions, torch::Tensor ret, torch::Tensor disc,
+    torch::Tensor has_next, double v_min, double v_max, bool dueling,
+    bool double_q, torch::Tensor weights);
 std::vector<torch::Tensor> dqn_loss_bwd(
     torch::Tensor logits_s, torch::Tensor actions, torch::Tensor dq,
     torch::Tensor gl, bool dueling);
+void per_ingest(torch::Tensor tree_sum, torch::Tensor tree_min,
+                torch::Tensor max_prio, int64_t start, int64_t count,
+                int64_t capacity, double alpha);
+std::vector<torch::Tensor> per_sample(
+    torch::Tensor tree_sum, torch::Tensor tree_min, torch::Tensor u,
+    int64_t capacity, double beta);
+void per_update(torch::Tensor tree_sum, torch::Tensor tree_min,
+                torch::Tensor max_prio, torch::Tensor idx,
+                torch::Tensor td_abs, int64_t capacity, double alpha,
+                double eps);
 void env_step_batch(std::vector<torch::Tensor> T, std::vector<double> fscal,
                     std::vector<int64_t> iscal);
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs);
@@ -179,7 +195,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "ring, bit-equal to nstep_transitions_reference");
     m.def("dqn_loss_fwd", &dqn_loss_fwd,
           "fused dueling double-DQN TD loss: row kernel, ordered reduction");
+    m.def("dqn_loss_fwd_weighted", &dqn_loss_fwd_weighted,
+          "importance-weighted DQN TD loss (prioritized replay); also "
+          "returns the unweighted |td| per row");
     m.def("dqn_loss_bwd", &dqn_loss_bwd, "analytic DQN loss backward");
+    m.def("per_ingest", &per_ingest,
+          "prioritized replay: new slots enter the sum/min trees at "
+          "max_prio^alpha");
+    m.def("per_sample", &per_sample,
+          "prioritized replay: sum-tree descent and importance weights");
+    m.def("per_update", &per_update,
+          "prioritized replay: new priorities for a minibatch's slots, "
+          "last occurrence wins");
     m.def("segment_mean_bwd", &segment_mean_bwd,
           "per-graph mean backward (broadcast/scale)");
     m.def("flat_adam", &flat_adam,

@@ -147,7 +147,11 @@ dqn_nstep_ingest_kernel(const float* __restrict__ gfull,     // [T*N, F]
 }
 
 // one wave per row (A <= 64).  rows_out[b] = {huber, q_a, |td|, target};
-// dq_out[b] = clamp(td, -1, 1), the Huber derivative.
+// dq_out[b] = clamp(td, -1, 1), the Huber derivative.  With importance
+// weights (prioritized replay; `weights` is null otherwise) the Huber term
+// and dq are multiplied by w[b], so the reduction gives mean(w * huber) and
+// the backward kernel is the same; q_a, |td| and target stay unweighted, and
+// |td| also goes to td_abs_out, the new priorities' input.
 __global__ void __launch_bounds__(BLOCK)
 dqn_row_kernel(const float* __restrict__ logits_s,    // [B, A] online, s
                const float* __restrict__ values_s,    // [B]
@@ -159,8 +163,10 @@ dqn_row_kernel(const float* __restrict__ logits_s,    // [B, A] online, s
                const float* __restrict__ ret,         // [B]
                const float* __restrict__ disc,        // [B]
                const float* __restrict__ has_next,    // [B]
+               const float* __restrict__ weights,     // [B] or null
                double* __restrict__ rows_out,         // [B, 4]
                double* __restrict__ dq_out,           // [B]
+               double* __restrict__ td_abs_out,       // [B] or null
                int B, int A, double v_min, double v_max, bool dueling,
                bool double_q) {
     const int wave = threadIdx.x / WAVE;
@@ -198,11 +204,19 @@ dqn_row_kernel(const float* __restrict__ logits_s,    // [B, A] online, s
         const double ad = fabs(td);
         const double huber = (ad < 1.0) ? 0.5 * td * td : ad - 0.5;
         if (lane == 0) {
-            rows_out[(long)b * 4 + 0] = huber;
+            const double dq = fmin(fmax(td, -1.0), 1.0);
+            if (weights != nullptr) {
+                const double w = (double)weights[b];
+                rows_out[(long)b * 4 + 0] = w * huber;
+                dq_out[b] = w * dq;
+            } else {
+                rows_out[(long)b * 4 + 0] = huber;
+                dq_out[b] = dq;
+            }
             rows_out[(long)b * 4 + 1] = q_a;
             rows_out[(long)b * 4 + 2] = ad;
             rows_out[(long)b * 4 + 3] = target;
-            dq_out[b] = fmin(fmax(td, -1.0), 1.0);
+            if (td_abs_out != nullptr) td_abs_out[b] = ad;
         }
     }
 }
@@ -349,19 +363,19 @@ int64_t dqn_nstep_ingest(
     return K;
 }
 
-// returns {loss[1], stats[4], dq[B] (f64)}; dq (with logits_s and actions)
-// is what dqn_loss_bwd needs
-std::vector<torch::Tensor> dqn_loss_fwd(
-    torch::Tensor logits_s, torch::Tensor values_s, torch::Tensor logits_no,
-    torch::Tensor values_no, torch::Tensor logits_nt, torch::Tensor values_nt,
-    torch::Tensor actions, torch::Tensor ret, torch::Tensor disc,
-    torch::Tensor has_next, double v_min, double v_max, bool dueling,
-    bool double_q) {
-    TORCH_CHECK(logits_s.dim() == 2, "dqn_loss_fwd: logits_s must be [B, A]");
+// weights: null for the plain loss.  Returns {loss[1], stats[4], dq[B] (f64)}
+// and, with weights, td_abs[B] (f64)
+static std::vector<torch::Tensor> dqn_loss_fwd_impl(
+    const char* name, torch::Tensor logits_s, torch::Tensor values_s,
+    torch::Tensor logits_no, torch::Tensor values_no, torch::Tensor logits_nt,
+    torch::Tensor values_nt, torch::Tensor actions, torch::Tensor ret,
+    torch::Tensor disc, torch::Tensor has_next, double v_min, double v_max,
+    bool dueling, bool double_q, const torch::Tensor* weights) {
+    TORCH_CHECK(logits_s.dim() == 2, name, ": logits_s must be [B, A]");
     const int64_t B = logits_s.size(0), A = logits_s.size(1);
-    TORCH_CHECK(B >= 1 && B < (1LL << 31), "dqn_loss_fwd: B out of range");
-    TORCH_CHECK(A >= 1 && A <= 64,
-                "dqn_loss_fwd needs A <= 64 (one wave per row)");
+    TORCH_CHECK(B >= 1 && B < (1LL << 31), name, ": B out of range");
+    TORCH_CHECK(A >= 1 && A <= 64, name,
+                " needs A <= 64 (one wave per row)");
     check_f32(logits_s, B * A, "dqn_loss_fwd logits_s");
     check_f32(values_s, B, "dqn_loss_fwd values_s");
     check_f32(logits_no, B * A, "dqn_loss_fwd logits_no");
@@ -372,12 +386,16 @@ std::vector<torch::Tensor> dqn_loss_fwd(
     check_f32(ret, B, "dqn_loss_fwd ret");
     check_f32(disc, B, "dqn_loss_fwd disc");
     check_f32(has_next, B, "dqn_loss_fwd has_next");
+    if (weights != nullptr)
+        check_f32(*weights, B, "dqn_loss_fwd_weighted weights");
     auto opt = logits_s.options();
     auto opt64 = opt.dtype(torch::kFloat64);
     auto rows = torch::empty({B, 4}, opt64);
     auto dq = torch::empty({B}, opt64);
     auto loss = torch::empty({1}, opt);
     auto stats = torch::empty({4}, opt);
+    torch::Tensor td_abs;
+    if (weights != nullptr) td_abs = torch::empty({B}, opt64);
     hipStream_t stream = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(dqn_row_kernel, dim3(row_blocks(B)), dim3(BLOCK), 0,
                        stream, logits_s.data_ptr<float>(),
@@ -387,13 +405,47 @@ std::vector<torch::Tensor> dqn_loss_fwd(
                        logits_nt.data_ptr<float>(),
                        values_nt.data_ptr<float>(), actions.data_ptr<long>(),
                        ret.data_ptr<float>(), disc.data_ptr<float>(),
-                       has_next.data_ptr<float>(), rows.data_ptr<double>(),
-                       dq.data_ptr<double>(), (int)B, (int)A, v_min, v_max,
-                       dueling, double_q);
+                       has_next.data_ptr<float>(),
+                       weights != nullptr ? weights->data_ptr<float>()
+                                          : (const float*)nullptr,
+                       rows.data_ptr<double>(), dq.data_ptr<double>(),
+                       weights != nullptr ? td_abs.data_ptr<double>()
+                                          : (double*)nullptr,
+                       (int)B, (int)A, v_min, v_max, dueling, double_q);
     hipLaunchKernelGGL(dqn_reduce_kernel, dim3(1), dim3(BLOCK), 0, stream,
                        rows.data_ptr<double>(), loss.data_ptr<float>(),
                        stats.data_ptr<float>(), (int)B);
+    if (weights != nullptr) return {loss, stats, dq, td_abs};
     return {loss, stats, dq};
+}
+
+// returns {loss[1], stats[4], dq[B] (f64)}; dq (with logits_s and actions)
+// is what dqn_loss_bwd needs
+std::vector<torch::Tensor> dqn_loss_fwd(
+    torch::Tensor logits_s, torch::Tensor values_s, torch::Tensor logits_no,
+    torch::Tensor values_no, torch::Tensor logits_nt, torch::Tensor values_nt,
+    torch::Tensor actions, torch::Tensor ret, torch::Tensor disc,
+    torch::Tensor has_next, double v_min, double v_max, bool dueling,
+    bool double_q) {
+    return dqn_loss_fwd_impl("dqn_loss_fwd", logits_s, values_s, logits_no,
+                             values_no, logits_nt, values_nt, actions, ret,
+                             disc, has_next, v_min, v_max, dueling, double_q,
+                             nullptr);
+}
+
+// the importance-weighted loss of prioritized replay: loss = mean(w * huber),
+// dq = w * clamp(td, -1, 1).  Returns {loss[1], stats[4], dq[B], td_abs[B]}
+// (the last two f64); td_abs is the unweighted |td| that per_update reads
+std::vector<torch::Tensor> dqn_loss_fwd_weighted(
+    torch::Tensor logits_s, torch::Tensor values_s, torch::Tensor logits_no,
+    torch::Tensor values_no, torch::Tensor logits_nt, torch::Tensor values_nt,
+    torch::Tensor actions, torch::Tensor ret, torch::Tensor disc,
+    torch::Tensor has_next, double v_min, double v_max, bool dueling,
+    bool double_q, torch::Tensor weights) {
+    return dqn_loss_fwd_impl("dqn_loss_fwd_weighted", logits_s, values_s,
+                             logits_no, values_no, logits_nt, values_nt,
+                             actions, ret, disc, has_next, v_min, v_max,
+                             dueling, double_q, &weights);
 }
 
 std::vector<torch::Tensor> dqn_loss_bwd(

@@ -11,8 +11,19 @@ Mapping onto this stack:
 - Exploration is Boltzmann over Q (Categorical(logits=Q)) so collection
   reuses the SAME rollout machinery as PPO/IMPALA (engine or subprocess
   workers); APEX's epsilon-greedy-per-worker and its distributed
-  prioritized replay shards are replaced by a uniform in-memory buffer —
-  divergences from APEX, not from DQN.
+  replay shards are replaced by one in-memory buffer — divergences from
+  APEX, not from DQN.
+- The buffer samples uniformly by default.  ``prioritized_replay=True``
+  turns on proportional prioritization with the reference's tuned
+  ``prioritized_replay_alpha`` 0.9, ``_beta`` 0.1 and ``_eps`` 1e-6: slots
+  are drawn in proportion to ``(|td| + eps) ** alpha`` from a sum tree, the
+  loss is ``mean(w * huber)`` with ``w = (p_i n) ** -beta / max_weight``,
+  and every minibatch's ``|td|`` becomes its slots' new priorities
+  (rl/device_replay.py; on a GPU the kernels of ops/hip/per_replay.hip).
+  Divergences that remain: new transitions enter at ``max_prio ** alpha``
+  (standard PER) where the reference's ``worker_side_prioritization``
+  computes an initial TD error; beta is constant; the tail of a fragment
+  (its last ``n_step`` rows) is still dropped.
 - Unlike the reference (which DISABLES action masking for DQN as a
   workaround for an RLlib crash, apex_dqn.yaml "TEMP HACK"), masking works
   here: invalid actions carry -inf Q and are never selected.
@@ -35,7 +46,7 @@ import torch
 import torch.nn.functional as F
 
 from ..parallel import all_reduce_gradients
-from .device_replay import DeviceReplay
+from .device_replay import DeviceReplay, SumTreeReference
 from .impala import LEARNERS, ImpalaTrainer
 from .rollout import CompactObs
 
@@ -61,6 +72,20 @@ class DQNConfig:
     # ring + fused TD-loss kernels (needs an env with
     # supports_device_resident, else falls back to "torch" with a warning)
     learner: str = "torch"
+    # proportional prioritized replay (both learners); the three values are
+    # the reference's tuned ones
+    prioritized_replay: bool = False
+    prioritized_replay_alpha: float = 0.9
+    prioritized_replay_beta: float = 0.1
+    prioritized_replay_eps: float = 1e-6
+
+    def __post_init__(self):
+        if self.prioritized_replay_alpha < 0:
+            raise ValueError("prioritized_replay_alpha must be >= 0")
+        if self.prioritized_replay_beta < 0:
+            raise ValueError("prioritized_replay_beta must be >= 0")
+        if not self.prioritized_replay_eps > 0:
+            raise ValueError("prioritized_replay_eps must be > 0")
 
 
 def nstep_transitions_reference(rewards, dones, n_step: int, gamma: float):
@@ -107,17 +132,24 @@ def dueling_q(logits, values, dueling: bool):
 
 
 STAT_KEYS = ("total_loss", "q_mean", "td_abs_mean", "target_mean")
+# what a prioritized update reports on top: the mean importance weight of the
+# update's minibatches and the largest priority |td| + eps seen so far
+PER_STAT_KEYS = ("is_weight_mean", "max_priority")
 
 
 def dqn_loss_reference(logits_s, values_s, logits_no, values_no, logits_nt,
                        values_nt, actions, ret, disc, has_next, v_min, v_max,
-                       dueling: bool, double_q: bool):
+                       dueling: bool, double_q: bool, weights=None):
     """The loss of ``DQNTrainer.update()`` as a torch autograd chain over
     whole-minibatch tensors.  ``logits_s`` [B, A] / ``values_s`` [B] are the
     online net on s and carry the graph; ``*_no`` / ``*_nt`` are the online
     and the target net on s' and are constants; ``has_next`` [B] is 0 where
     the n-step return was cut, and such a row bootstraps from 0 whatever its
-    s' rows hold.  Returns (loss, dict of 0-d stat tensors in STAT_KEYS)."""
+    s' rows hold.  Returns (loss, dict of 0-d stat tensors in STAT_KEYS).
+
+    With ``weights`` [B] (prioritized replay's importance weights) the loss
+    is ``mean(weights * huber)``, the other stats stay unweighted, and the
+    dict also carries ``td_abs`` [B], the rows' ``|q_a - target|``."""
     with torch.no_grad():
         q_next_t = dueling_q(logits_nt, values_nt, dueling)
         if double_q:
@@ -129,11 +161,18 @@ def dqn_loss_reference(logits_s, values_s, logits_no, values_no, logits_nt,
         target = torch.clamp(ret + disc * boot, v_min, v_max)
     q = dueling_q(logits_s, values_s, dueling)
     q_a = q.gather(1, actions.unsqueeze(1)).squeeze(1)
-    loss = F.smooth_l1_loss(q_a, target)
-    return loss, {"total_loss": loss.detach(),
-                  "q_mean": q_a.detach().mean(),
-                  "td_abs_mean": (q_a.detach() - target).abs().mean(),
-                  "target_mean": target.mean()}
+    if weights is None:
+        loss = F.smooth_l1_loss(q_a, target)
+    else:
+        loss = (weights * F.smooth_l1_loss(q_a, target,
+                                           reduction="none")).mean()
+    stats = {"total_loss": loss.detach(),
+             "q_mean": q_a.detach().mean(),
+             "td_abs_mean": (q_a.detach() - target).abs().mean(),
+             "target_mean": target.mean()}
+    if weights is not None:
+        stats["td_abs"] = (q_a.detach() - target).abs()
+    return loss, stats
 
 
 class _DQNLossFn(torch.autograd.Function):
@@ -169,6 +208,34 @@ class _DQNLossFn(torch.autograd.Function):
         return (glogits, gvalues) + (None,) * 12
 
 
+class _DQNWeightedLossFn(torch.autograd.Function):
+    """``_DQNLossFn`` with importance weights (``dqn_loss_fwd_weighted``):
+    loss = mean(w * huber) and the saved dq carries w, so the backward kernel
+    is the same one.  Returns (loss, stats[4], td_abs[B] f64 unweighted)."""
+
+    @staticmethod
+    def forward(ctx, logits_s, values_s, logits_no, values_no, logits_nt,
+                values_nt, actions, ret, disc, has_next, v_min, v_max,
+                dueling, double_q, weights):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        logits_s = logits_s.contiguous()
+        loss, stats, dq, td_abs = ext.dqn_loss_fwd_weighted(
+            logits_s, values_s.contiguous(), logits_no.contiguous(),
+            values_no.contiguous(), logits_nt.contiguous(),
+            values_nt.contiguous(), actions, ret, disc, has_next,
+            float(v_min), float(v_max), bool(dueling), bool(double_q),
+            weights.contiguous())
+        ctx.save_for_backward(logits_s, actions, dq)
+        ctx.dueling = bool(dueling)
+        ctx.mark_non_differentiable(stats, td_abs)
+        return loss.reshape(()), stats, td_abs
+
+    @staticmethod
+    def backward(ctx, gl, _gstats, _gtd):
+        return _DQNLossFn.backward(ctx, gl, _gstats) + (None,)
+
+
 class DQNTrainer(ImpalaTrainer):
     """Same trainer-facing interface as PPOTrainer/ImpalaTrainer."""
 
@@ -191,6 +258,11 @@ class DQNTrainer(ImpalaTrainer):
         self._replay_ptr = 0
         # the device learner's ring, made on the first device-resident batch
         self.replay_dev: Optional[DeviceReplay] = None
+        # the torch learner's priorities when prioritized_replay is on: a
+        # host sum tree over the list's slots (slot k % capacity, as the list
+        # fills and then overwrites)
+        self._per_host: Optional[SumTreeReference] = None
+        self._replay_written = 0
 
     # Q(s, .) with the dueling recombination over masked actions
     def _q_values(self, obs: List[CompactObs], net):
@@ -257,10 +329,11 @@ class DQNTrainer(ImpalaTrainer):
                 torch.log(gfull[:, 17:]), min=torch.finfo(torch.float32).min)
         return logits, values
 
-    def _loss_device(self, mb: Dict, target_emb):
+    def _loss_device(self, mb: Dict, target_emb, weights=None):
         """(loss, stats[4] tensor in STAT_KEYS order) of one ring minibatch:
         the fused kernels on a GPU, the torch chain on CPU tensors (the
-        CpuEngine backend)."""
+        CpuEngine backend).  With importance ``weights`` the loss is weighted
+        and a third value is the rows' unweighted |td| in f64."""
         from ..models.gnn import graph_mean
         cfg = self.config
         mb_static = self.env._models_batch
@@ -277,20 +350,32 @@ class DQNTrainer(ImpalaTrainer):
                 values_nt, mb["action"], mb["ret"], mb["disc"],
                 mb["has_next"], cfg.v_min, cfg.v_max, cfg.dueling,
                 cfg.double_q)
+        if weights is None:
+            if logits_s.is_cuda:
+                return _DQNLossFn.apply(*args)
+            loss, st = dqn_loss_reference(*args)
+            return loss, torch.stack([st[k] for k in STAT_KEYS])
         if logits_s.is_cuda:
-            return _DQNLossFn.apply(*args)
-        loss, st = dqn_loss_reference(*args)
-        return loss, torch.stack([st[k] for k in STAT_KEYS])
+            return _DQNWeightedLossFn.apply(*args, weights)
+        loss, st = dqn_loss_reference(*args, weights=weights)
+        return (loss, torch.stack([st[k] for k in STAT_KEYS]),
+                st["td_abs"].double())
 
     def _update_device(self, data: Dict) -> Dict[str, float]:
         from ..models.gnn import graph_mean
         cfg = self.config
         if self.replay_dev is None:
-            self.replay_dev = DeviceReplay(cfg.replay_capacity,
-                                           data["gfull_dev"].shape[1],
-                                           data["gfull_dev"].device)
+            self.replay_dev = DeviceReplay(
+                cfg.replay_capacity, data["gfull_dev"].shape[1],
+                data["gfull_dev"].device,
+                prioritized=cfg.prioritized_replay,
+                alpha=cfg.prioritized_replay_alpha,
+                beta=cfg.prioritized_replay_beta,
+                eps=cfg.prioritized_replay_eps)
         replay = self.replay_dev
         replay.ingest(data, cfg.n_step, cfg.gamma)
+        if cfg.prioritized_replay:
+            return self._update_device_prioritized(data)
         stats = {k: 0.0 for k in STAT_KEYS}
         if len(replay) >= cfg.learning_starts and cfg.num_sgd_iter > 0:
             rng = np.random.RandomState(self.iteration)
@@ -322,6 +407,65 @@ class DQNTrainer(ImpalaTrainer):
         self._sync_target(data)
         return stats
 
+    def _update_device_prioritized(self, data: Dict) -> Dict[str, float]:
+        """``_update_device`` after the ingest, with prioritized sampling:
+        per minibatch sample -> gather -> weighted loss -> step ->
+        update_priorities, all on the ring's device, and still one D2H per
+        update."""
+        from ..models.gnn import graph_mean
+        cfg = self.config
+        replay = self.replay_dev
+        keys = STAT_KEYS + PER_STAT_KEYS
+        stats = {k: 0.0 for k in keys}
+        if len(replay) >= cfg.learning_starts and cfg.num_sgd_iter > 0:
+            rng = np.random.RandomState(self.iteration)
+            # the torch learner's uniforms, uploaded once
+            u = torch.as_tensor(
+                rng.random_sample((cfg.num_sgd_iter, cfg.sgd_minibatch_size)),
+                device=replay.device)
+            with torch.no_grad():
+                mb_static = self.env._models_batch
+                target_emb = graph_mean(self.target.gnn(mb_static), mb_static)
+            acc = torch.zeros(len(STAT_KEYS) + 1, device=replay.device)
+            for k in range(cfg.num_sgd_iter):
+                idx, weight = replay.sample(u[k])
+                loss, stats_t, td_abs = self._loss_device(
+                    replay.gather(idx), target_emb, weights=weight)
+                self.optimizer.zero_grad(set_to_none=True)
+                loss.backward()
+                all_reduce_gradients(self.policy.parameters())
+                if cfg.grad_clip is not None:
+                    torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
+                                                   cfg.grad_clip)
+                self.optimizer.step()
+                replay.update_priorities(idx, td_abs)
+                acc[:len(STAT_KEYS)] += stats_t.detach()
+                acc[len(STAT_KEYS)] += weight.mean()
+            # one D2H for all stats of all minibatches and max_prio
+            out = torch.cat([acc.double() / cfg.num_sgd_iter,
+                             replay.max_prio])
+            stats = dict(zip(keys, out.tolist()))
+        stats["replay"] = len(replay)
+        stats["learner"] = 1
+        self._sync_target(data)
+        return stats
+
+    def _ingest_priorities(self, data: Dict):
+        """The torch learner's tree after ``_ingest(data)``: the list slots
+        the fragment wrote enter at ``max_prio ** alpha``."""
+        cfg = self.config
+        C = cfg.replay_capacity
+        if self._per_host is None:
+            self._per_host = SumTreeReference(
+                C, cfg.prioritized_replay_alpha, cfg.prioritized_replay_beta,
+                cfg.prioritized_replay_eps)
+        T, N = data["rewards"].shape
+        K = max(T - cfg.n_step, 0) * N
+        if K > 0:
+            self._per_host.ingest(
+                (self._replay_written + max(K - C, 0)) % C, min(K, C))
+        self._replay_written += K
+
     def _sync_target(self, data: Dict):
         # target sync on an env-step cadence (reference: 100k tuned)
         self._steps_since_sync += int(np.prod(data["rewards"].shape))
@@ -334,14 +478,26 @@ class DQNTrainer(ImpalaTrainer):
         if self._device_learner() and "gfull_dev" in data:
             return self._update_device(data)
         self._ingest(data)
+        per = None
+        if cfg.prioritized_replay:
+            self._ingest_priorities(data)
+            per = self._per_host
         if len(self.replay) < cfg.learning_starts:
             return {"total_loss": 0.0, "q_mean": 0.0,
                     "replay": len(self.replay), "learner": 0}
         rng = np.random.RandomState(self.iteration)
         stats = {"total_loss": 0.0, "q_mean": 0.0}
+        if per is not None:
+            stats["is_weight_mean"] = 0.0
+            # the device learner's uniforms
+            u = rng.random_sample((cfg.num_sgd_iter, cfg.sgd_minibatch_size))
         n_updates = 0
-        for _ in range(cfg.num_sgd_iter):
-            idx = rng.randint(0, len(self.replay), size=cfg.sgd_minibatch_size)
+        for it in range(cfg.num_sgd_iter):
+            if per is None:
+                idx = rng.randint(0, len(self.replay),
+                                  size=cfg.sgd_minibatch_size)
+            else:
+                idx, weight = per.sample(u[it])
             batch = [self.replay[i] for i in idx]
             s = [b[0] for b in batch]
             a = torch.as_tensor([b[1] for b in batch], device=self.device)
@@ -368,7 +524,12 @@ class DQNTrainer(ImpalaTrainer):
                 target = torch.clamp(r + disc * boot, cfg.v_min, cfg.v_max)
             q = self._q_values(s, self.policy)
             q_a = q.gather(1, a.unsqueeze(1)).squeeze(1)
-            loss = F.smooth_l1_loss(q_a, target)
+            if per is None:
+                loss = F.smooth_l1_loss(q_a, target)
+            else:
+                w = torch.as_tensor(weight, device=self.device)
+                loss = (w * F.smooth_l1_loss(q_a, target,
+                                             reduction="none")).mean()
             self.optimizer.zero_grad(set_to_none=True)
             loss.backward()
             all_reduce_gradients(self.policy.parameters())
@@ -376,11 +537,18 @@ class DQNTrainer(ImpalaTrainer):
                 torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
                                                cfg.grad_clip)
             self.optimizer.step()
+            if per is not None:
+                per.update(idx, (q_a.detach() - target).abs().double()
+                           .cpu().numpy())
+                stats["is_weight_mean"] += float(weight.mean())
             stats["total_loss"] += float(loss.item())
             stats["q_mean"] += float(q_a.mean().item())
             n_updates += 1
         for k in ("total_loss", "q_mean"):
             stats[k] /= max(n_updates, 1)
+        if per is not None:
+            stats["is_weight_mean"] /= max(n_updates, 1)
+            stats["max_priority"] = float(per.max_prio[0])
         stats["replay"] = len(self.replay)
         stats["learner"] = 0
         self._sync_target(data)

@@ -213,7 +213,12 @@ def build_trainer_from_config(cfg: dict, device=None):
             train_batch_size=algo.get("train_batch_size", 4096),
             sgd_minibatch_size=algo.get("sgd_minibatch_size", 256),
             num_sgd_iter=algo.get("num_sgd_iter", 4),
-            learner=str(algo.get("learner", "torch")))
+            learner=str(algo.get("learner", "torch")),
+            prioritized_replay=bool(algo.get("prioritized_replay", False)),
+            prioritized_replay_alpha=algo.get(
+                "prioritized_replay_alpha", 0.9),
+            prioritized_replay_beta=algo.get("prioritized_replay_beta", 0.1),
+            prioritized_replay_eps=algo.get("prioritized_replay_eps", 1e-6))
         return DQNTrainer(venv, policy, dq, device=device)
     if algo.get("name", "ppo") == "pg":
         from ..rl.pg import PGConfig, PGTrainer

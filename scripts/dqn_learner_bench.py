@@ -18,8 +18,16 @@ The timer is a host clock around each phase, and each phase ends in
 update under the torch profiler and reports the number of kernels it
 launched.  GPU only.
 
+``--prioritized`` runs both learners with ``prioritized_replay`` on (the
+yaml's alpha, beta and eps): the device learner with the sum-tree kernels of
+ops/hip/per_replay.hip, the torch learner with the host numpy tree.  The
+launch count then also reports the ``per_`` kernels, expected to be
+1 + 2 * num_sgd_iter per update (one ``per_ingest_kernel``, and per minibatch
+one ``per_sample_kernel`` and one ``per_update_kernel``): 9 at the yaml's
+num_sgd_iter = 4.
+
 Usage: python scripts/dqn_learner_bench.py [--envs 256] [--iters 10]
-           [--warmup 2] [--count-launches] [--out FILE]
+           [--warmup 2] [--prioritized] [--count-launches] [--out FILE]
 """
 import argparse
 import json
@@ -49,6 +57,8 @@ def main():
                     help="timed iterations per learner")
     ap.add_argument("--warmup", type=int, default=2,
                     help="untimed iterations per learner")
+    ap.add_argument("--prioritized", action="store_true",
+                    help="prioritized replay in both learners")
     ap.add_argument("--count-launches", action="store_true")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
@@ -91,7 +101,12 @@ def main():
             v_min=algo["v_min"], v_max=algo["v_max"],
             train_batch_size=algo["train_batch_size"],
             sgd_minibatch_size=algo["sgd_minibatch_size"],
-            num_sgd_iter=algo["num_sgd_iter"], learner=learner), device=dev)
+            num_sgd_iter=algo["num_sgd_iter"], learner=learner,
+            prioritized_replay=args.prioritized,
+            prioritized_replay_alpha=algo["prioritized_replay_alpha"],
+            prioritized_replay_beta=algo["prioritized_replay_beta"],
+            prioritized_replay_eps=algo["prioritized_replay_eps"]),
+            device=dev)
 
     trainers = {"torch": trainer("torch"), "device": trainer("device")}
     sync = torch.cuda.synchronize
@@ -124,7 +139,8 @@ def main():
     out = {"envs": args.envs, "steps_per_iteration": steps,
            "sgd_minibatch_size": algo["sgd_minibatch_size"],
            "num_sgd_iter": algo["num_sgd_iter"], "n_step": algo["n_step"],
-           "iters": args.iters, "warmup": args.warmup}
+           "iters": args.iters, "warmup": args.warmup,
+           "prioritized": args.prioritized}
     for name in trainers:
         assert last[name]["learner"] == (1 if name == "device" else 0)
         assert last[name]["total_loss"] > 0, "the timed updates must train"
@@ -132,6 +148,9 @@ def main():
                      "rollout_time_s": summary(rollout[name]),
                      "replay": last[name]["replay"],
                      "total_loss": last[name]["total_loss"]}
+        if args.prioritized:
+            out[name]["is_weight_mean"] = last[name]["is_weight_mean"]
+            out[name]["max_priority"] = last[name]["max_priority"]
     out["update_time_ratio_torch_over_device"] = (
         out["torch"]["update_time_s"]["mean"]
         / out["device"]["update_time_s"]["mean"])
@@ -171,7 +190,14 @@ def main():
     out["device_update_launches"] = {
         "kernels": len(names),
         "dqn_kernels": sum(n.startswith("dqn_") for n in names),
-        "per_minibatch": (len(names) - 1) / algo["num_sgd_iter"]}
+        # less the ingest (and, prioritized, the per_ingest) launch
+        "per_minibatch": (len(names) - (2 if args.prioritized else 1))
+        / algo["num_sgd_iter"]}
+    if args.prioritized:
+        out["device_update_launches"]["per_kernels"] = sum(
+            n.startswith("per_") for n in names)
+        out["device_update_launches"]["per_kernels_expected"] = \
+            1 + 2 * algo["num_sgd_iter"]
     emit()
 
 
