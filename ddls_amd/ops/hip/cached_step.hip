@@ -49,6 +49,13 @@
 // cs_bwd_w are one, and cs_bwd_w_reduce's sums are formed by the first
 // kernel of the optimiser tail when the caller defers them: 12 per replay.
 //
+// By default the two longest of those twelve run with shorter chains
+// (DDLS_AMD_STEP_HEAD, sections "cs_head with a shorter chain" and
+// "cs_bwd_pool_wfc with shorter roles" below): cs_head2 in place of cs_head
+// and cs_bwd_pool_wfc2 in place of cs_bwd_pool_wfc, the same launches with
+// the same outputs in the same bits.  DDLS_AMD_STEP_HEAD=off launches the
+// two kernels they replace.
+//
 // DDLS_AMD_STEP_FUSION=off launches the previous 20 separate kernels and
 // DDLS_AMD_ROW_KERNELS=thread the thread-per-row ones before them; both
 // sets stay in this file unchanged as oracles for bitwise comparison.
@@ -2101,6 +2108,324 @@ cs_head_kernel(CachedPtrs P, CachedDims D) {
   // statistics blocks of cs_bwd_scat1_gu1_kernel
 }
 
+// ---- cs_head with a shorter chain (DDLS_AMD_STEP_HEAD, default on) ----
+// cs_head_kernel's phases, arithmetic and stores, term for term; the kernel
+// above stays unchanged as the oracle.  What changes is what sits on the
+// block's serial chain:
+//  * every per-sample input of a chunk (mask, actions, old_logp, adv, vtarg)
+//    is loaded at the chunk's top, in the round trip of gf / model_ids, not
+//    in the middle of the chain (logf(mask) is taken there too);
+//  * the gfinal phase reads its W1p / W1v copies i-major ([i][j], row stride
+//    HD2_WS) and the hidden-grad rows with 16-byte LDS reads: 4 reads per
+//    four j instead of 16.  The chain order stays j = 0..255, policy term
+//    then value term, all fused.  Thread j writes column j of the copies, so
+//    the writes are conflict-free;
+//  * one sample a block on min(B, HD2_MAXB) blocks instead of four on
+//    min(B, 32): the FC-hidden, logit-partial and hidden-grad phases are as
+//    many times as long per thread as a block has samples in flight, and the
+//    other CUs idle anyway.  The chunk loop and the [HS] row buffers are the
+//    oracle's, with HS = 1; traces of 4, 2 and 1 samples a block at B = 128
+//    are in docs/KERNELS.md, "Round 9".
+#define HD2_WS (KFC + 4)           // 16-byte aligned, rows 4 banks apart
+#define HD2_MAXB 128
+#define LDS4(p) (*reinterpret_cast<const float4*>(p))   // 16-byte LDS read
+__global__ void __launch_bounds__(256)
+cs_head2_kernel(CachedPtrs P, CachedDims D) {
+  constexpr int HS = 1;              // samples in flight per block
+  __shared__ float sW2p[KA * HD_ROW];
+  __shared__ __align__(16) float sW1p[KFIN * HD2_WS], sW1v[KFIN * HD2_WS];
+  __shared__ float sWg[KGE * KGF];
+  __shared__ float sB2p[KA];
+  __shared__ float sGL[HS][KA], sGV[HS], sGF[HS][KFIN];
+  __shared__ __align__(16) float sGHp[HS][HD2_WS], sGHv[HS][HD2_WS];
+  // forward rows
+  __shared__ float sFin[HS][KFIN], sHp[HS][HD_ROW], sVred[HS][KFC];
+  __shared__ float sGf[HS][KGF], sU34[HS][KGF];
+  __shared__ float sGamG[KGF], sBetG[KGF], sBg[KGE];
+  __shared__ float sPart[HS][KA][16 + 1];
+  __shared__ float sRow[HS][KA], sPp[HS][KA], sLp[HS][KA];
+  __shared__ float sVal[HS], sCoef[HS], sHent[HS];
+  const int tid = threadIdx.x;
+  constexpr int NT = 256;
+  for (int x = tid; x < KA * KFC; x += NT)
+    sW2p[(x / KFC) * HD_ROW + hd_pad(x % KFC)] = WP(W_P2_W)[x];
+  for (int x = tid; x < KGE * KGF; x += NT) sWg[x] = WP(W_G_W)[x];
+  if (tid < KA) sB2p[tid] = WP(W_P2_B)[tid];
+  if (tid < KGF) {
+    sGamG[tid] = WP(W_LN_G_W)[tid];
+    sBetG[tid] = WP(W_LN_G_B)[tid];
+  }
+  if (tid < KGE) sBg[tid] = WP(W_G_B)[tid];
+  float w1p[KFIN], w1v[KFIN];
+#pragma unroll
+  for (int i = 0; i < KFIN; ++i) {
+    w1p[i] = WP(W_P1_W)[tid * KFIN + i];
+    w1v[i] = WP(W_V1_W)[tid * KFIN + i];
+  }
+  // the backward's LDS copy of W1p / W1v, i-major: thread j writes column j
+#pragma unroll
+  for (int i = 0; i < KFIN; ++i) {
+    sW1p[i * HD2_WS + tid] = w1p[i];
+    sW1v[i * HD2_WS + tid] = w1v[i];
+  }
+  const float b1p = WP(W_P1_B)[tid], b1v = WP(W_V1_B)[tid];
+  const float w2v = WP(W_V2_W)[tid];
+  const float b2v = WP(W_V2_B)[0];
+  const float klc = P.kl[0];
+  const int wv = tid >> 6, ln = tid & 63;
+  const int per = (D.B + gridDim.x - 1) / gridDim.x;
+  const int b0 = blockIdx.x * per;
+  const int b1 = min(D.B, b0 + per);
+  for (int c0 = b0; c0 < b1; c0 += HS) {
+    const int ns = min(HS, b1 - c0);
+    // per-sample inputs of the chunk, clamped instead of branched on: row
+    // thread x = (s, a) its mask entry and its sample's action; lane 0 of
+    // wave s the loss row's scalars; thread 128 + s the value target
+    const int xr_ = min(tid, ns * KA - 1);
+    const float r_mask = P.mask[(long)c0 * KA + xr_];
+    const long r_act = P.actions[c0 + xr_ / KA];
+    const int bw_ = c0 + min(wv, ns - 1);
+    const long w_act = P.actions[bw_];
+    const float w_old_lp = P.old_logp[bw_];
+    const float w_adv = P.adv[bw_];
+    const float r_vtarg = P.vtarg[c0 + min(max(tid - 128, 0), ns - 1)];
+    for (int x = tid; x < ns * KGF; x += NT)
+      sGf[x / KGF][x % KGF] = P.gf[(long)c0 * KGF + x];
+    for (int x = tid; x < ns * KOUT; x += NT) {
+      const int s = x / KOUT, i = x % KOUT;
+      const long mid = P.model_ids[c0 + s];
+      const float pv = P.pooled[mid * KOUT + i];
+      sFin[s][i] = pv;
+      P.fin[(long)(c0 + s) * KFIN + i] = pv;
+    }
+    const float fmin = -3.402823466e+38f;
+    float r_lm = logf(r_mask);
+    if (!(r_lm > fmin)) r_lm = fmin;
+    __syncthreads();
+    for (int x = tid; x < ns * KGF; x += NT) {
+      const int s = x / KGF, i = x % KGF;
+      const float* __restrict__ xr = sGf[s];
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < KGF; ++k) sum = sum + xr[k];
+      const float mu = sum / KGF;
+      float var;
+      {
+        const float d0 = xr[0] - mu;
+        var = d0 * d0;
+      }
+#pragma unroll
+      for (int k = 1; k < KGF; ++k) {
+        const float d = xr[k] - mu;
+        var = var + d * d;
+      }
+      const float rstd = rsqrtf(var / KGF + LN_EPS);
+      const float xh = (xr[i] - mu) * rstd;
+      P.xh34[(long)(c0 + s) * KGF + i] = xh;
+      sU34[s][i] = FMA(xh, sGamG[i], sBetG[i]);
+    }
+    __syncthreads();
+    for (int x = tid; x < ns * KGE; x += NT) {
+      const int s = x / KGE, o = x % KGE;
+      float acc = sBg[o];
+#pragma unroll
+      for (int i = 0; i < KGF; ++i)
+        acc = FMA(sWg[o * KGF + i], sU34[s][i], acc);
+      sFin[s][KOUT + o] = acc;               // graph_module has NO activation
+      P.fin[(long)(c0 + s) * KFIN + KOUT + o] = acc;
+    }
+    __syncthreads();
+    // FC hidden layers: bias first, i ascending
+    float hp[HS], hv[HS];
+#pragma unroll
+    for (int s = 0; s < HS; ++s) {
+      hp[s] = 0.f;
+      hv[s] = 0.f;
+      if (s < ns) {
+        float ap = b1p, av = b1v;
+#pragma unroll
+        for (int i = 0; i < KFIN; ++i) {
+          ap = FMA(w1p[i], sFin[s][i], ap);
+          av = FMA(w1v[i], sFin[s][i], av);
+        }
+        ap = ap > 0.f ? ap : 0.f;
+        av = av > 0.f ? av : 0.f;
+        const long u = (long)(c0 + s) * KFC + tid;
+        P.h1p[u] = ap;
+        P.h1v[u] = av;
+        hp[s] = ap;
+        hv[s] = av;
+        sHp[s][hd_pad(tid)] = ap;
+        sVred[s][tid] = w2v * av;
+      }
+    }
+    __syncthreads();
+    // logit partials over the 16 chunks of the hidden row
+    for (int x = tid; x < ns * KA * 16; x += NT) {
+      const int s = x / (KA * 16), r = x % (KA * 16);
+      const int a = r / 16, c = r % 16;
+      const float* __restrict__ w = sW2p + a * HD_ROW + c * HD_CS;
+      const float* __restrict__ h = sHp[s] + c * HD_CS;
+      float acc = FMA(w[0], h[0], 0.f);
+#pragma unroll
+      for (int i = 1; i < 16; ++i) {
+        if (i < 4) acc = FMA(w[i], h[i], acc);
+        else acc = acc + w[i] * h[i];
+      }
+      sPart[s][a][c] = acc;
+    }
+    // value: wave s folds sample s's 256 products in the halving tree's
+    // pairing (t with t + 128, 64, ... 1)
+    if (wv < ns) {
+      const float* __restrict__ vr = sVred[wv];
+      float a0 = vr[ln] + vr[ln + 128];
+      const float a1 = vr[ln + 64] + vr[ln + 192];
+      a0 = a0 + a1;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1)
+        a0 = a0 + __shfl_down(a0, off, 64);
+      if (ln == 0) {
+        const float val = a0 + b2v;
+        sVal[wv] = val;
+        P.values[c0 + wv] = val;
+      }
+    }
+    __syncthreads();
+    // raw masked logits
+    if (tid < ns * KA) {
+      const int s = tid / KA, a = tid % KA;
+      float acc = sB2p[a];
+#pragma unroll
+      for (int c = 0; c < 16; ++c) acc = acc + sPart[s][a][c];
+      sRow[s][a] = acc + r_lm;
+    }
+    __syncthreads();
+    // softmax / surrogate row of sample s: lane 0 of wave s
+    if (wv < ns && ln == 0) {
+      const int s = wv;
+      const int b = c0 + s;
+      const float* __restrict__ row = sRow[s];
+      float mx = -3.0e38f;
+#pragma unroll
+      for (int a = 0; a < KA; ++a) mx = fmaxf(mx, row[a]);
+      float Z = 0.f;
+#pragma unroll
+      for (int a = 0; a < KA; ++a) Z = Z + __expf(row[a] - mx);
+      const float lse = mx + __logf(Z);
+      float ent = 0.f;
+#pragma unroll
+      for (int a = 0; a < KA; ++a) {
+        const float lp = row[a] - lse;
+        const float e = __expf(lp);
+        sLp[s][a] = lp;
+        sPp[s][a] = e;
+        ent = FMA(-lp, e, ent);
+      }
+      const float logp_a = sLp[s][w_act];
+      const float ratio = __expf(logp_a - w_old_lp);
+      const float A_b = w_adv;
+      const float r_cl = fminf(fmaxf(ratio, 1.f - D.clip), 1.f + D.clip);
+      const float surr1 = ratio * A_b, surr2 = r_cl * A_b;
+      float ds = ratio * A_b;
+      if (surr2 < surr1 && (ratio < 1.f - D.clip || ratio > 1.f + D.clip))
+        ds = 0.f;
+      const float coef = -ds - klc;
+      P.hent[b] = ent;
+      P.coef[b] = coef;
+      sHent[s] = ent;
+      sCoef[s] = coef;
+    }
+    __syncthreads();
+    // loss backward rows (upstream grad = 1); p and lp go out here
+    if (tid < ns * KA) {
+      const int s = tid / KA, a = tid % KA;
+      const int b = c0 + s;
+      const long u = (long)b * KA + a;
+      const float c = sCoef[s] / D.B;
+      const float pj = sPp[s][a];
+      const float lpj = sLp[s][a];
+      P.p[u] = pj;
+      P.lp[u] = lpj;
+      const float delta = (a == (int)r_act) ? 1.f : 0.f;
+      const float gl = mul_rn(c, delta - pj)
+                       + mul_rn(mul_rn(D.ent_coef / D.B, pj),
+                                lpj + sHent[s]);
+      P.glogits[u] = gl;
+      sGL[s][a] = gl;
+    }
+    if (tid >= 128 && tid < 128 + ns) {
+      const int s = tid - 128;
+      const int b = c0 + s;
+      const float verr = sVal[s] - r_vtarg;
+      const float mk = (verr * verr <= D.vf_clip) ? 1.f : 0.f;
+      const float gv = D.vf_coef * 2.f * verr * mk / D.B;
+      P.gvalue[b] = gv;
+      sGV[s] = gv;
+    }
+    __syncthreads();
+    // hidden grads
+#pragma unroll
+    for (int s = 0; s < HS; ++s) {
+      if (s < ns) {
+        const int j = tid;
+        const long u = (long)(c0 + s) * KFC + j;
+        float acc = 0.f;
+#pragma unroll
+        for (int a = 0; a < KA; ++a) {
+          // the first five terms are fused, the rest rounded products
+          const float w = sW2p[a * HD_ROW + hd_pad(j)];
+          if (a < 5) acc = FMA(w, sGL[s][a], acc);
+          else acc = acc + mul_rn(w, sGL[s][a]);
+        }
+        const float gp = hp[s] > 0.f ? acc : 0.f;
+        const float av = w2v * sGV[s];
+        const float gv = hv[s] > 0.f ? av : 0.f;
+        P.gh1p[u] = gp;
+        P.gh1v[u] = gv;
+        sGHp[s][j] = gp;
+        sGHv[s][j] = gv;
+      }
+    }
+    __syncthreads();
+    // gfinal: one thread per (sample, i), j = 0..FC-1 in order, four j a read
+    if (tid < ns * KFIN) {
+      const int s = tid / KFIN, i = tid % KFIN;
+      const float* __restrict__ wp = sW1p + i * HD2_WS;
+      const float* __restrict__ wvv = sW1v + i * HD2_WS;
+      const float* __restrict__ gp = sGHp[s];
+      const float* __restrict__ gv = sGHv[s];
+      float acc = 0.f;
+#pragma unroll 4
+      for (int j = 0; j < KFC; j += 4) {
+        const float4 a = LDS4(wp + j), b = LDS4(wvv + j);
+        const float4 g = LDS4(gp + j), h = LDS4(gv + j);
+        acc = FMA(a.x, g.x, acc);
+        acc = FMA(b.x, h.x, acc);
+        acc = FMA(a.y, g.y, acc);
+        acc = FMA(b.y, h.y, acc);
+        acc = FMA(a.z, g.z, acc);
+        acc = FMA(b.z, h.z, acc);
+        acc = FMA(a.w, g.w, acc);
+        acc = FMA(b.w, h.w, acc);
+      }
+      P.gfinal[(long)(c0 + s) * KFIN + i] = acc;
+      sGF[s][i] = acc;
+    }
+    __syncthreads();
+    // graph-module LN-out grads
+    for (int x = tid; x < ns * KGF; x += NT) {
+      const int s = x / KGF, i = x % KGF;
+      float acc = 0.f;
+#pragma unroll
+      for (int o = 0; o < KGE; ++o)
+        acc = acc + mul_rn(sWg[o * KGF + i], sGF[s][KOUT + o]);
+      P.gu34[(long)(c0 + s) * KGF + i] = acc;
+    }
+    // The next chunk's first barrier separates these reads from the next
+    // writes of the row buffers, as in cs_head_kernel.
+  }
+}
+
 // ---- cs_fwd_combine<2> + the per-model means of cs_fwd_pool ----
 // One block per model: its nodes' h2 rows are computed into the LDS tile
 // (and written out), then unit i adds them in node order, as a chain out of
@@ -2725,6 +3050,471 @@ cs_bwd_pool_wfc_kernel(CachedPtrs P, CachedDims D) {
   }
 }
 
+// ---- cs_bwd_pool_wfc with shorter roles (DDLS_AMD_STEP_HEAD, default on) ----
+// Same launch, same outputs, same bits as cs_bwd_pool_wfc_kernel above, which
+// stays unchanged as the oracle (DDLS_AMD_STEP_HEAD=off launches it).  The
+// launch lasts as long as its slowest block, and every role's time is issue
+// slots of one wave: LDS reads and dependent FMAs.  What changes:
+//
+//  * FC-column role: WFC2_JW columns a block instead of 16 (KFC / WFC2_JW
+//    blocks instead of 16), so no thread carries more than one weight unit,
+//    and the weight units, the W2p units and the single-chain sums sit in
+//    different waves where the block has room.  Columns are independent
+//    outputs: no partial sums, no reduce, every chain keeps its term order.
+//  * Sample-major tiles are stored transposed ([column][sample], row stride
+//    WFC2_TS), so a chain reads four consecutive samples of an operand with
+//    one 16-byte LDS read: 3 reads + 8 FMAs per four terms of a W1p/W1v unit
+//    instead of 12 + 8.  The terms are still consumed in sample order.
+//  * Graph-module role: the same transposed layout and 16-byte reads.
+//  * Pool role: wave 0 lists the model's samples once, in sample order, and
+//    the chain then adds only those.  The oracle adds +0 for every other
+//    sample.  Its accumulator starts at +0, and a round-to-nearest sum is -0
+//    only when both addends are -0, so the accumulator is never -0 and adding
+//    +0 to it never changes it: leaving those terms out gives the same bits.
+//  * The weight slot offsets are loaded once at the top of a block, in the
+//    same round trip as the first tile, not in front of the final stores.
+//
+// Tile pattern of the W2p units as in the oracle: the super-tile is walked in
+// TILE_K-row tiles; a full tile's terms 0-19 are fused and 20-31 are rounded
+// products, a partial tile is fused throughout.
+#define WFC2_JW 4                       // FC columns per block
+#define WFC2_NFC (KFC / WFC2_JW)        // FC-column blocks
+#define WFC2_TS (WFC_ST + 4)            // transposed row stride (16 B aligned)
+#define WFC2_LDS_POOL (2 * 1024 + WFC_ST * KOUT + KOUT + 16)
+#define WFC2_LDS_G (WFC2_TS * (KGE + 3 * KGF))
+#define WFC2_LDS_FC (WFC2_TS * (KFIN + 4 * WFC2_JW + KA + 1))
+#define WFC2_LDS (WFC2_LDS_G > WFC2_LDS_FC ? WFC2_LDS_G : WFC2_LDS_FC)
+static_assert(WFC2_LDS >= WFC2_LDS_POOL, "pool role LDS");
+static_assert(WFC2_LDS * 4 <= 64 * 1024, "cs_bwd_pool_wfc2: LDS over 64 KB");
+static_assert(WFC2_JW % 4 == 0 && KFC % WFC2_JW == 0, "whole float4 columns");
+static_assert(WFC2_JW * KFIN <= 256, "one weight unit a thread");
+static_assert(WFC_ST % 64 == 0 && SG_MAXB % WFC_ST == 0, "tiles of whole waves");
+static_assert(TILE_K == 32, "20 fused + 12 rounded terms a full tile");
+
+__global__ void __launch_bounds__(256)
+cs_bwd_pool_wfc2_kernel(CachedPtrs P, CachedDims D) {
+  __shared__ __align__(16) float lds[WFC2_LDS];
+  const int tid = threadIdx.x;
+  constexpr int NT = 256;
+  constexpr int TS = WFC2_TS;
+  const int bid = blockIdx.x;
+
+  if (bid < D.M) {
+    // ---- pool role: gpool[m] and this model's gh2 rows ----
+    const int m = bid;
+    int* smid = reinterpret_cast<int*>(lds);            // [1024]
+    int* slist = smid + 1024;                           // [1024] members
+    float (*sG)[KOUT] = reinterpret_cast<float (*)[KOUT]>(lds + 2048);
+    float* sP = lds + 2048 + WFC_ST * KOUT;             // [KOUT]
+    int* send = reinterpret_cast<int*>(sP + KOUT);      // [SG_MAXB / WFC_ST]
+    const long lo = P.model_nptr[m], hi = P.model_nptr[m + 1];
+    for (int b = tid; b < D.B; b += NT) smid[b] = (int)P.model_ids[b];
+    float acc = 0.f;
+    int k = 0;
+    for (int t0 = 0; t0 < D.B; t0 += WFC_ST) {
+      const int bt = min(WFC_ST, D.B - t0);
+      float rG[WFC_ST * KOUT / NT];
+#pragma unroll
+      for (int q = 0; q < WFC_ST * KOUT / NT; ++q) {
+        const int x = min(tid + q * NT, bt * KOUT - 1);
+        rG[q] = P.gfinal[(long)(t0 + x / KOUT) * KFIN + x % KOUT];
+      }
+      __syncthreads();
+      if (t0 == 0 && tid < 64) {
+        // the model's samples in sample order; send[t]: how many of them lie
+        // in super-tiles 0..t
+        int cnt = 0;
+        for (int b0 = 0; b0 < D.B; b0 += 64) {
+          const int b = b0 + tid;
+          const bool mine = b < D.B && smid[min(b, D.B - 1)] == m;
+          const unsigned long long bal = __ballot(mine);
+          if (mine) slist[cnt + __popcll(bal & ((1ull << tid) - 1ull))] = b;
+          cnt += __popcll(bal);
+          if (tid == 0 && ((b0 + 64) % WFC_ST == 0 || b0 + 64 >= D.B))
+            send[b0 / WFC_ST] = cnt;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < WFC_ST * KOUT / NT; ++q) {
+        const int x = tid + q * NT;
+        if (x < bt * KOUT) sG[x / KOUT][x % KOUT] = rG[q];
+      }
+      __syncthreads();
+      if (tid < KOUT) {
+        const int k1 = send[t0 / WFC_ST];
+#pragma unroll 4
+        for (; k < k1; ++k) acc += sG[slist[k] - t0][tid];
+      }
+    }
+    if (tid < KOUT) {
+      P.gpool[(long)m * KOUT + tid] = acc;
+      sP[tid] = acc;
+    }
+    __syncthreads();
+    const float nn = (float)(hi - lo);
+    for (long u = lo * KOUT + tid; u < hi * KOUT; u += NT)
+      P.gh2[u] = sP[u % KOUT] / nn;
+    return;
+  }
+
+  if (bid == D.M) {
+    // ---- graph module: Wg[GEMB,GFin], bg; LN gamma/beta from gu34 + xh34.
+    // gpre rows are gfinal[:, KOUT:KOUT+KGE] (row stride KFIN).
+    float* tG = lds;                                    // [KGE][TS]
+    float* tU = tG + KGE * TS;                          // [KGF][TS]
+    float* tXH = tU + KGF * TS;                         // [KGF][TS]
+    float* tGU = tXH + KGF * TS;                        // [KGF][TS]
+    const long o_gam = P.offs[W_LN_G_W], o_bet = P.offs[W_LN_G_B];
+    const long o_w = P.offs[W_G_W], o_b = P.offs[W_G_B];
+    const float* __restrict__ gam = P.flat_p + o_gam;
+    const float* __restrict__ bet = P.flat_p + o_bet;
+    constexpr int UNITS = KGE * KGF;
+    constexpr int MYU = (UNITS + 255) / 256;
+    float acc[MYU];
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) acc[q] = 0.f;
+    // tid in [64, 64+KGE): bias sums; tid in [128, 128+KGF): LN gamma;
+    // tid in [192, 192+KGF): LN beta
+    float bacc = 0.f, lacc = 0.f;
+    for (int r0 = 0; r0 < D.B; r0 += WFC_ST) {
+      const int rt = min(WFC_ST, D.B - r0);
+      {
+        constexpr int CX = WFC_ST * KGF / NT;
+        static_assert(WFC_ST * KGE / 4 == NT && CX * NT == WFC_ST * KGF,
+                      "whole trips");
+        float rXH[CX], rGU[CX], rGam[CX], rBet[CX];
+        // one 16-byte load a thread: row tid / 2, half tid % 2 of gpre
+        const int gx = min(tid, rt * (KGE / 4) - 1);
+        const float4 rG = *reinterpret_cast<const float4*>(
+            P.gfinal + (long)(r0 + gx / (KGE / 4)) * KFIN + KOUT
+            + 4 * (gx % (KGE / 4)));
+#pragma unroll
+        for (int k = 0; k < CX; ++k) {
+          const int x = min(tid + k * NT, rt * KGF - 1);
+          rXH[k] = P.xh34[(long)r0 * KGF + x];
+          rGU[k] = P.gu34[(long)r0 * KGF + x];
+          rGam[k] = gam[x % KGF];
+          rBet[k] = bet[x % KGF];
+        }
+        if (tid < rt * (KGE / 4)) {
+          const int t = tid / (KGE / 4), c = 4 * (tid % (KGE / 4));
+          tG[(c + 0) * TS + t] = rG.x;
+          tG[(c + 1) * TS + t] = rG.y;
+          tG[(c + 2) * TS + t] = rG.z;
+          tG[(c + 3) * TS + t] = rG.w;
+        }
+#pragma unroll
+        for (int k = 0; k < CX; ++k) {
+          const int x = tid + k * NT;
+          if (x < rt * KGF) {
+            const int t = x / KGF, i = x % KGF;
+            tU[i * TS + t] = FMA(rXH[k], rGam[k], rBet[k]);
+            tXH[i * TS + t] = rXH[k];
+            tGU[i * TS + t] = rGU[k];
+          }
+        }
+      }
+      __syncthreads();
+      const int rt4 = rt & ~3;
+#pragma unroll
+      for (int q = 0; q < MYU; ++q) {
+        int u = tid + q * 256;
+        if (u < UNITS) {
+          const float* go = tG + (u / KGF) * TS;
+          const float* ui = tU + (u % KGF) * TS;
+          float a = acc[q];
+          if (rt == WFC_ST) {
+#pragma unroll 8
+            for (int t = 0; t < WFC_ST; t += 4) {
+              const float4 g = LDS4(go + t), v = LDS4(ui + t);
+              a = FMA(g.x, v.x, a);
+              a = FMA(g.y, v.y, a);
+              a = FMA(g.z, v.z, a);
+              a = FMA(g.w, v.w, a);
+            }
+          } else {
+            for (int t = 0; t < rt4; t += 4) {
+              const float4 g = LDS4(go + t), v = LDS4(ui + t);
+              a = FMA(g.x, v.x, a);
+              a = FMA(g.y, v.y, a);
+              a = FMA(g.z, v.z, a);
+              a = FMA(g.w, v.w, a);
+            }
+            for (int t = rt4; t < rt; ++t) a = FMA(go[t], ui[t], a);
+          }
+          acc[q] = a;
+        }
+      }
+      if (tid >= 64 && tid < 64 + KGE) {
+        const float* go = tG + (tid - 64) * TS;
+        for (int t = 0; t < rt4; t += 4) {
+          const float4 g = LDS4(go + t);
+          bacc = bacc + g.x;
+          bacc = bacc + g.y;
+          bacc = bacc + g.z;
+          bacc = bacc + g.w;
+        }
+        for (int t = rt4; t < rt; ++t) bacc = bacc + go[t];
+      }
+      if (tid >= 128 && tid < 128 + KGF) {
+        const float* gu = tGU + (tid - 128) * TS;
+        const float* xh = tXH + (tid - 128) * TS;
+        for (int t = 0; t < rt4; t += 4) {
+          const float4 g = LDS4(gu + t), x = LDS4(xh + t);
+          lacc = lacc + mul_rn(g.x, x.x);
+          lacc = lacc + mul_rn(g.y, x.y);
+          lacc = lacc + mul_rn(g.z, x.z);
+          lacc = lacc + mul_rn(g.w, x.w);
+        }
+        for (int t = rt4; t < rt; ++t) lacc = lacc + mul_rn(gu[t], xh[t]);
+      }
+      if (tid >= 192 && tid < 192 + KGF) {
+        const float* gu = tGU + (tid - 192) * TS;
+        for (int t = 0; t < rt4; t += 4) {
+          const float4 g = LDS4(gu + t);
+          lacc = lacc + g.x;
+          lacc = lacc + g.y;
+          lacc = lacc + g.z;
+          lacc = lacc + g.w;
+        }
+        for (int t = rt4; t < rt; ++t) lacc = lacc + gu[t];
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < MYU; ++q) {
+      int u = tid + q * 256;
+      if (u < UNITS) P.flat_g[o_w + u] = acc[q];
+    }
+    if (tid >= 64 && tid < 64 + KGE) P.flat_g[o_b + tid - 64] = bacc;
+    if (tid >= 128 && tid < 128 + KGF) P.flat_g[o_gam + tid - 128] = lacc;
+    if (tid >= 192 && tid < 192 + KGF) P.flat_g[o_bet + tid - 192] = lacc;
+    return;
+  }
+
+  // ---- FC-column jobs: block jb owns columns [j0, j0 + JW) of W1p/W1v
+  // [FC,FIN] (+ b1p/b1v) AND of W2p [A,FC] / W2v [FC]; block 0 also sums b2p
+  // and b2v.
+  {
+    constexpr int JW = WFC2_JW;
+    constexpr int PV = JW * KFIN;       // W1p/W1v units: tid in [0, PV)
+    constexpr int A2 = KA * JW;         // W2p units: tid in [A2_T0, A2_T0+A2)
+    constexpr int A2_T0 = PV <= 128 ? 128 : NT - A2;
+    constexpr int CS_N = 2 * JW;        // b1p, b1v column sums: tid < CS_N
+    constexpr int W2V_T0 = PV;          // W2v columns: tid in [PV, PV+JW)
+    constexpr int B2_T0 = NT - 32;      // jb == 0: b2p rows, then b2v
+    static_assert(A2_T0 >= 0 && A2_T0 + A2 <= NT && W2V_T0 + JW <= NT
+                  && KA + 1 <= 32, "roles fit the block");
+    const int jb = bid - D.M - 1;
+    if (jb >= WFC2_NFC) return;
+    const int j0 = jb * JW;
+    float* tF = lds;                                    // [KFIN][TS]
+    float* tGp = tF + KFIN * TS;                        // [JW][TS]
+    float* tGv = tGp + JW * TS;                         // [JW][TS], after tGp
+    float* tHp = tGv + JW * TS;                         // [JW][TS]
+    float* tHv = tHp + JW * TS;                         // [JW][TS]
+    float* tGL = tHv + JW * TS;                         // [KA + 1][TS]; row KA
+                                                        // is gvalue
+    const long o_p1w = P.offs[W_P1_W], o_v1w = P.offs[W_V1_W];
+    const long o_p2w = P.offs[W_P2_W], o_p1b = P.offs[W_P1_B];
+    const long o_v1b = P.offs[W_V1_B], o_v2w = P.offs[W_V2_W];
+    const long o_p2b = P.offs[W_P2_B], o_v2b = P.offs[W_V2_B];
+    float ap = 0.f, av = 0.f, s2 = 0.f, cs = 0.f, w2v = 0.f, b2 = 0.f;
+    const bool is_pv = tid < PV;
+    const bool is_a2 = tid >= A2_T0 && tid < A2_T0 + A2;
+    const bool is_cs = tid < CS_N;
+    const bool is_w2v = tid >= W2V_T0 && tid < W2V_T0 + JW;
+    const bool is_b2 = jb == 0 && tid >= B2_T0 && tid < B2_T0 + KA + 1;
+    const int pj = tid / KFIN, pi = tid % KFIN;
+    const int aa = (tid - A2_T0) / JW, aj = (tid - A2_T0) % JW;
+    for (int s0 = 0; s0 < D.B; s0 += WFC_ST) {
+      const int st = min(WFC_ST, D.B - s0);
+      // all global loads of the super-tile first (clamped indices, one basic
+      // block), then the transposed LDS stores
+      {
+        constexpr int CF = WFC_ST * KFIN / 4 / NT;      // float4 a thread
+        constexpr int CL = (WFC_ST * KA + NT - 1) / NT;
+        constexpr int Q = JW / 4;                       // float4 a column row
+        static_assert(CF * NT * 4 == WFC_ST * KFIN && WFC_ST * Q <= NT
+                      && WFC_ST <= NT, "whole trips");
+        float4 rF[CF];
+        float rGL[CL];
+#pragma unroll
+        for (int k = 0; k < CF; ++k) {
+          const int x = min(tid + k * NT, st * (KFIN / 4) - 1);
+          rF[k] = *reinterpret_cast<const float4*>(
+              P.fin + (long)s0 * KFIN + 4 * x);
+        }
+        const int cx = min(tid, st * Q - 1);
+        const long cg = (long)(s0 + cx / Q) * KFC + j0 + 4 * (cx % Q);
+        const float4 rGp = *reinterpret_cast<const float4*>(P.gh1p + cg);
+        const float4 rGv = *reinterpret_cast<const float4*>(P.gh1v + cg);
+        const float4 rHp = *reinterpret_cast<const float4*>(P.h1p + cg);
+        const float4 rHv = *reinterpret_cast<const float4*>(P.h1v + cg);
+#pragma unroll
+        for (int k = 0; k < CL; ++k) {
+          const int x = min(tid + k * NT, st * KA - 1);
+          rGL[k] = P.glogits[(long)s0 * KA + x];
+        }
+        const float rGV = P.gvalue[s0 + min(tid, st - 1)];
+#pragma unroll
+        for (int k = 0; k < CF; ++k) {
+          const int x = tid + k * NT;
+          if (x < st * (KFIN / 4)) {
+            const int t = x / (KFIN / 4), c = 4 * (x % (KFIN / 4));
+            tF[(c + 0) * TS + t] = rF[k].x;
+            tF[(c + 1) * TS + t] = rF[k].y;
+            tF[(c + 2) * TS + t] = rF[k].z;
+            tF[(c + 3) * TS + t] = rF[k].w;
+          }
+        }
+        if (tid < st * Q) {
+          const int t = tid / Q, c = 4 * (tid % Q);
+          tGp[(c + 0) * TS + t] = rGp.x;
+          tGp[(c + 1) * TS + t] = rGp.y;
+          tGp[(c + 2) * TS + t] = rGp.z;
+          tGp[(c + 3) * TS + t] = rGp.w;
+          tGv[(c + 0) * TS + t] = rGv.x;
+          tGv[(c + 1) * TS + t] = rGv.y;
+          tGv[(c + 2) * TS + t] = rGv.z;
+          tGv[(c + 3) * TS + t] = rGv.w;
+          tHp[(c + 0) * TS + t] = rHp.x;
+          tHp[(c + 1) * TS + t] = rHp.y;
+          tHp[(c + 2) * TS + t] = rHp.z;
+          tHp[(c + 3) * TS + t] = rHp.w;
+          tHv[(c + 0) * TS + t] = rHv.x;
+          tHv[(c + 1) * TS + t] = rHv.y;
+          tHv[(c + 2) * TS + t] = rHv.z;
+          tHv[(c + 3) * TS + t] = rHv.w;
+        }
+#pragma unroll
+        for (int k = 0; k < CL; ++k) {
+          const int x = tid + k * NT;
+          if (x < st * KA) tGL[(x % KA) * TS + x / KA] = rGL[k];
+        }
+        if (tid < st) tGL[KA * TS + tid] = rGV;
+      }
+      __syncthreads();
+      const int st4 = st & ~3;
+      if (is_pv) {
+        // W1p / W1v unit (pj, pi): sample order, fused throughout
+        const float* fr = tF + pi * TS;
+        const float* gp = tGp + pj * TS;
+        const float* gv = tGv + pj * TS;
+        if (st == WFC_ST) {
+#pragma unroll 8
+          for (int t = 0; t < WFC_ST; t += 4) {
+            const float4 f = LDS4(fr + t), a = LDS4(gp + t), b = LDS4(gv + t);
+            ap = FMA(a.x, f.x, ap);
+            av = FMA(b.x, f.x, av);
+            ap = FMA(a.y, f.y, ap);
+            av = FMA(b.y, f.y, av);
+            ap = FMA(a.z, f.z, ap);
+            av = FMA(b.z, f.z, av);
+            ap = FMA(a.w, f.w, ap);
+            av = FMA(b.w, f.w, av);
+          }
+        } else {
+          for (int t = 0; t < st4; t += 4) {
+            const float4 f = LDS4(fr + t), a = LDS4(gp + t), b = LDS4(gv + t);
+            ap = FMA(a.x, f.x, ap);
+            av = FMA(b.x, f.x, av);
+            ap = FMA(a.y, f.y, ap);
+            av = FMA(b.y, f.y, av);
+            ap = FMA(a.z, f.z, ap);
+            av = FMA(b.z, f.z, av);
+            ap = FMA(a.w, f.w, ap);
+            av = FMA(b.w, f.w, av);
+          }
+          for (int t = st4; t < st; ++t) {
+            ap = FMA(gp[t], fr[t], ap);
+            av = FMA(gv[t], fr[t], av);
+          }
+        }
+      }
+      if (is_a2) {
+        // W2p unit (aa, aj), tile by tile as the oracle's chain saw them
+        const float* gl = tGL + aa * TS;
+        const float* hp = tHp + aj * TS;
+        for (int r0 = 0; r0 < st; r0 += TILE_K) {
+          const int rt = min(TILE_K, st - r0);
+          if (rt == TILE_K) {
+#pragma unroll
+            for (int t = 0; t < TILE_K; t += 4) {
+              const float4 g = LDS4(gl + r0 + t), h = LDS4(hp + r0 + t);
+              if (t < 20) {
+                s2 = FMA(g.x, h.x, s2);
+                s2 = FMA(g.y, h.y, s2);
+                s2 = FMA(g.z, h.z, s2);
+                s2 = FMA(g.w, h.w, s2);
+              } else {
+                s2 = s2 + mul_rn(g.x, h.x);
+                s2 = s2 + mul_rn(g.y, h.y);
+                s2 = s2 + mul_rn(g.z, h.z);
+                s2 = s2 + mul_rn(g.w, h.w);
+              }
+            }
+          } else {
+            for (int t = 0; t < rt; ++t)
+              s2 = FMA(gl[r0 + t], hp[r0 + t], s2);
+          }
+        }
+      }
+      if (is_cs) {
+        // b1p (tid < JW) and b1v column sums: rows of tGp, then of tGv
+        const float* g = tGp + tid * TS;
+        for (int t = 0; t < st4; t += 4) {
+          const float4 v = LDS4(g + t);
+          cs = cs + v.x;
+          cs = cs + v.y;
+          cs = cs + v.z;
+          cs = cs + v.w;
+        }
+        for (int t = st4; t < st; ++t) cs = cs + g[t];
+      }
+      if (is_w2v) {
+        const float* gvl = tGL + KA * TS;
+        const float* hv = tHv + (tid - W2V_T0) * TS;
+        for (int t = 0; t < st4; t += 4) {
+          const float4 g = LDS4(gvl + t), h = LDS4(hv + t);
+          w2v = FMA(g.x, h.x, w2v);
+          w2v = FMA(g.y, h.y, w2v);
+          w2v = FMA(g.z, h.z, w2v);
+          w2v = FMA(g.w, h.w, w2v);
+        }
+        for (int t = st4; t < st; ++t) w2v = FMA(gvl[t], hv[t], w2v);
+      }
+      if (is_b2) {
+        // b2p rows 0..KA-1 of glogits, b2v row KA (gvalue)
+        const float* g = tGL + (tid - B2_T0) * TS;
+        for (int t = 0; t < st4; t += 4) {
+          const float4 v = LDS4(g + t);
+          b2 = b2 + v.x;
+          b2 = b2 + v.y;
+          b2 = b2 + v.z;
+          b2 = b2 + v.w;
+        }
+        for (int t = st4; t < st; ++t) b2 = b2 + g[t];
+      }
+      __syncthreads();
+    }
+    if (is_pv) {
+      P.flat_g[o_p1w + (long)(j0 + pj) * KFIN + pi] = ap;
+      P.flat_g[o_v1w + (long)(j0 + pj) * KFIN + pi] = av;
+    }
+    if (is_a2) P.flat_g[o_p2w + (long)aa * KFC + j0 + aj] = s2;
+    if (is_cs) {
+      if (tid < JW) P.flat_g[o_p1b + j0 + tid] = cs;
+      else P.flat_g[o_v1b + j0 + tid - JW] = cs;
+    }
+    if (is_w2v) P.flat_g[o_v2w + j0 + tid - W2V_T0] = w2v;
+    if (is_b2) {
+      if (tid - B2_T0 < KA) P.flat_g[o_p2b + tid - B2_T0] = b2;
+      else P.flat_g[o_v2b] = b2;
+    }
+  }
+}
+
 // ---- cs_stage + cs_fwd_mlp_lanes<1> ----
 // Block 0 gathers the minibatch from the device batch store (the body of
 // cs_stage_kernel, one workgroup, same cursor protocol and guards); blocks
@@ -3328,6 +4118,12 @@ cs_bwd_scat1_gu1_w_kernel(CachedPtrs P, CachedDims D) {
 //                                launched by cached_step_bwd (oracle / A/B);
 //                                STEP_OVERLAP=off, STEP_FUSION=off and
 //                                'thread' imply it
+//   DDLS_AMD_STEP_HEAD=off       cs_head and cs_bwd_pool_wfc in place of
+//                                cs_head2 and cs_bwd_pool_wfc2 (oracle /
+//                                A/B); STEP_MERGE=off and whatever implies it
+//                                imply this too.  The new kernels do not
+//                                depend on DDLS_AMD_WGRAD_MFMA and stay the
+//                                default with it.
 struct RowCfg {
   bool thread;
   int lanes;   // 0: per-kernel default
@@ -3336,6 +4132,7 @@ struct RowCfg {
                  // (needs the fused launches)
   bool merge;    // launches merged along row-local dependencies (needs
                  // overlap)
+  bool head;     // cs_head2 / cs_bwd_pool_wfc2 (needs merge)
 };
 
 static RowCfg row_cfg() {
@@ -3372,6 +4169,12 @@ static RowCfg row_cfg() {
               "cached_step: DDLS_AMD_STEP_MERGE must be 'on' or 'off', got '",
               sm, "'");
   c.merge = !moff && c.overlap;
+  const char* sh = getenv("DDLS_AMD_STEP_HEAD");
+  const bool hoff = (sh != nullptr && strcmp(sh, "off") == 0);
+  TORCH_CHECK(sh == nullptr || sh[0] == '\0' || hoff || strcmp(sh, "on") == 0,
+              "cached_step: DDLS_AMD_STEP_HEAD must be 'on' or 'off', got '",
+              sh, "'");
+  c.head = !hoff && c.merge;
   return c;
 }
 
@@ -3607,10 +4410,17 @@ static void step_fwd_launches(const CachedPtrs& P, const CachedDims& D,
     if (D.M > 0)
       hipLaunchKernelGGL(cs_fwd_comb2_pool_kernel, dim3(D.M), dim3(256), 0,
                          stream, P, D);
-    const int hb = D.B < 32 ? D.B : 32;
-    if (hb > 0)
-      hipLaunchKernelGGL(cs_head_kernel, dim3(hb), dim3(256), 0, stream,
-                         P, D);
+    // one sample a block (cs_head2) or four (cs_head, the oracle)
+    const int hb = R.head ? (D.B < HD2_MAXB ? D.B : HD2_MAXB)
+                          : (D.B < 32 ? D.B : 32);
+    if (hb > 0) {
+      if (R.head)
+        hipLaunchKernelGGL(cs_head2_kernel, dim3(hb), dim3(256), 0, stream,
+                           P, D);
+      else
+        hipLaunchKernelGGL(cs_head_kernel, dim3(hb), dim3(256), 0, stream,
+                           P, D);
+    }
     return;
   }
   hipLaunchKernelGGL(cs_fwd_combine_kernel<2>, dim3(comb2_b), dim3(256), 0,
@@ -3715,7 +4525,17 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs,
   if (!R.fused)
     hipLaunchKernelGGL(cs_bwd_head_kernel, dim3(hb), dim3(256), 0, stream,
                        P, D);
-  if (R.overlap)
+  if (R.head) {
+    // the same roles in shorter blocks; its 16-byte loads need these rows
+    // aligned (every scratch tensor is an allocation of its own)
+    for (const float* q : {(const float*)P.fin, (const float*)P.gfinal,
+                           (const float*)P.gh1p, (const float*)P.gh1v,
+                           (const float*)P.h1p, (const float*)P.h1v})
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(q) % 16 == 0,
+                  "cached_step: head scratch tensors must be 16-byte aligned");
+    hipLaunchKernelGGL(cs_bwd_pool_wfc2_kernel, dim3(D.M + 1 + WFC2_NFC),
+                       dim3(256), 0, stream, P, D);
+  } else if (R.overlap)
     // one pool block per model + the graph-module block + the FC-column
     // blocks, which cs_bwd_w below then does not launch
     hipLaunchKernelGGL(cs_bwd_pool_wfc_kernel, dim3(D.M + 1 + WFC_NFC),
