@@ -108,6 +108,16 @@ std::vector<torch::Tensor> dqn_loss_fwd_weighted(
 std::vector<torch::Tensor> dqn_loss_bwd(
     torch::Tensor logits_s, torch::Tensor actions, torch::Tensor dq,
     torch::Tensor gl, bool dueling);
+std::vector<torch::Tensor> dqn_head_step_fwd(
+    std::vector<torch::Tensor> ring, torch::Tensor idx,
+    torch::Tensor model_emb, torch::Tensor target_emb,
+    std::vector<torch::Tensor> online, std::vector<torch::Tensor> target,
+    double v_min, double v_max, bool dueling, bool double_q,
+    c10::optional<torch::Tensor> weights,
+    c10::optional<torch::Tensor> err_acc, bool validate);
+std::vector<torch::Tensor> dqn_head_step_bwd(
+    std::vector<torch::Tensor> saved, std::vector<torch::Tensor> online,
+    torch::Tensor gl, int64_t M, bool dueling);
 void per_ingest(torch::Tensor tree_sum, torch::Tensor tree_min,
                 torch::Tensor max_prio, int64_t start, int64_t count,
                 int64_t capacity, double alpha);
@@ -199,6 +209,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "importance-weighted DQN TD loss (prioritized replay); also "
           "returns the unweighted |td| per row");
     m.def("dqn_loss_bwd", &dqn_loss_bwd, "analytic DQN loss backward");
+    m.def("dqn_head_step_fwd", &dqn_head_step_fwd,
+          "fused DQN Q-head minibatch step: three head passes read through "
+          "idx from the replay ring, TD loss, ordered reduction");
+    m.def("dqn_head_step_bwd", &dqn_head_step_bwd,
+          "analytic backward of dqn_head_step_fwd into the online head "
+          "tensors and model_emb (MFMA weight-grad tiles)");
     m.def("per_ingest", &per_ingest,
           "prioritized replay: new slots enter the sum/min trees at "
           "max_prio^alpha");

@@ -35,6 +35,12 @@ chain.  ``"device"`` trains from the flat device tensors of
 ``DeviceReplay`` ring, the forward is head-only and never touches
 ``data["obs"]``, and on a GPU the loss is the fused kernels of
 ``ops/hip/dqn_loss.hip`` with one D2H per update for the stats.
+
+``DQNConfig.head_step="fused"`` (device learner only) replaces the gather,
+the three head passes, the loss and their autograd backward by the kernels of
+``ops/hip/dqn_head_step.hip``: three launches forward and two backward per
+minibatch, reading the ring through the minibatch's slot indices.  The GNN
+forward and backward and the optimizer stay as they are.
 """
 from __future__ import annotations
 
@@ -49,6 +55,9 @@ from ..parallel import all_reduce_gradients
 from .device_replay import DeviceReplay, SumTreeReference
 from .impala import LEARNERS, ImpalaTrainer
 from .rollout import CompactObs
+
+
+HEAD_STEPS = ("torch", "fused")
 
 
 @dataclass
@@ -78,8 +87,15 @@ class DQNConfig:
     prioritized_replay_alpha: float = 0.9
     prioritized_replay_beta: float = 0.1
     prioritized_replay_eps: float = 1e-6
+    # the device learner's Q-head step.  "torch": gather + three _heads
+    # passes + the fused loss.  "fused": the kernels of
+    # ops/hip/dqn_head_step.hip (policy._fused_head_ok shapes only)
+    head_step: str = "torch"
 
     def __post_init__(self):
+        if self.head_step not in HEAD_STEPS:
+            raise ValueError("DQNConfig.head_step must be 'torch' or "
+                             f"'fused', not {self.head_step!r}")
         if self.prioritized_replay_alpha < 0:
             raise ValueError("prioritized_replay_alpha must be >= 0")
         if self.prioritized_replay_beta < 0:
@@ -236,6 +252,102 @@ class _DQNWeightedLossFn(torch.autograd.Function):
         return _DQNLossFn.backward(ctx, gl, _gstats) + (None,)
 
 
+def head_tensors(policy):
+    """The head's live parameters in ``head_params`` order (those carry the
+    autograd graph; ``head_params`` detaches)."""
+    ln, lin_g = policy.graph_module[0], policy.graph_module[1]
+    pb, vb = policy.policy_branch, policy.value_branch
+    return [ln.weight, ln.bias, lin_g.weight, lin_g.bias,
+            pb[0].weight, pb[0].bias, pb[2].weight, pb[2].bias,
+            vb[0].weight, vb[0].bias, vb[2].weight, vb[2].bias]
+
+
+def _heads_functional(head, model_emb, gfull, model_ids):
+    """``DQNTrainer._heads`` on the 12 head tensors instead of a module (a
+    ``_fused_head_ok`` policy: one graph layer, hiddens [256], ReLU, mask)."""
+    graph_emb = F.linear(F.layer_norm(gfull, gfull.shape[-1:], head[0],
+                                      head[1]), head[2], head[3])
+    final = torch.cat([model_emb[model_ids], graph_emb], dim=-1)
+    logits = F.linear(F.relu(F.linear(final, head[4], head[5])),
+                      head[6], head[7])
+    values = F.linear(F.relu(F.linear(final, head[8], head[9])),
+                      head[10], head[11]).squeeze(-1)
+    logits = logits + torch.clamp(torch.log(gfull[:, 17:]),
+                                  min=torch.finfo(torch.float32).min)
+    return logits, values
+
+
+def dqn_head_step_reference(ring, idx, model_emb, target_emb, online, target,
+                            v_min, v_max, dueling: bool, double_q: bool,
+                            weights=None):
+    """One minibatch step of the Q-head as a plain torch chain, in the dtype
+    of its inputs: the three head passes on the ring rows ``idx`` (``ring`` in
+    ``RING_KEYS`` order, ``online`` / ``target`` in ``head_params`` order),
+    then ``dqn_loss_reference``.  Differentiable in ``model_emb`` and
+    ``online`` through the pass on s only.  Returns (loss, stats[4] in
+    STAT_KEYS order) and, with ``weights``, the rows' |td| in f64."""
+    s_gfull, s_model, action, ret, disc, has_next, n_gfull, n_model = (
+        t.index_select(0, idx) for t in ring)
+    logits_s, values_s = _heads_functional(online, model_emb, s_gfull,
+                                           s_model)
+    with torch.no_grad():
+        logits_no, values_no = _heads_functional(
+            online, model_emb.detach(), n_gfull, n_model)
+        logits_nt, values_nt = _heads_functional(target, target_emb, n_gfull,
+                                                 n_model)
+    loss, st = dqn_loss_reference(
+        logits_s, values_s, logits_no, values_no, logits_nt, values_nt,
+        action, ret, disc, has_next, v_min, v_max, dueling, double_q,
+        weights=weights)
+    stats = torch.stack([st[k] for k in STAT_KEYS])
+    if weights is None:
+        return loss, stats
+    return loss, stats, st["td_abs"].double()
+
+
+class _DQNHeadStepFn(torch.autograd.Function):
+    """Fused Q-head minibatch step (ops/hip/dqn_head_step.hip): three
+    launches forward, two backward.  ``ring`` and ``target`` are lists of
+    constants; ``model_emb`` and the 12 ``online`` head tensors take a
+    gradient.  Returns (loss, stats[4]) or, with ``weights``, (loss, stats,
+    td_abs[B] f64).  ``err`` (int32 [1], optional) is OR-ed with the device
+    validation flag so a caller can read it with its other results; without
+    it the call validates at once, which costs a host sync."""
+
+    @staticmethod
+    def forward(ctx, ring, idx, model_emb, target_emb, target, v_min, v_max,
+                dueling, double_q, weights, err, *online):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        online_c = [t.detach().contiguous() for t in online]
+        out = ext.dqn_head_step_fwd(
+            list(ring), idx, model_emb.detach().contiguous(),
+            target_emb.detach().contiguous(), online_c,
+            [t.detach().contiguous() for t in target], float(v_min),
+            float(v_max), bool(dueling), bool(double_q),
+            None if weights is None else weights.contiguous(), err,
+            err is None)
+        loss, stats = out[0], out[1]
+        ctx.save_for_backward(*out[3:11], *online_c)
+        ctx.dueling = bool(dueling)
+        ctx.num_models = model_emb.shape[0]
+        if weights is None:
+            ctx.mark_non_differentiable(stats)
+            return loss.reshape(()), stats
+        ctx.mark_non_differentiable(stats, out[11])
+        return loss.reshape(()), stats, out[11]
+
+    @staticmethod
+    def backward(ctx, gl, *_unused):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        saved, online = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        grads = ext.dqn_head_step_bwd(
+            list(saved), list(online), gl.reshape(1).contiguous(),
+            ctx.num_models, ctx.dueling)
+        return (None, None, grads[12]) + (None,) * 8 + tuple(grads[:12])
+
+
 class DQNTrainer(ImpalaTrainer):
     """Same trainer-facing interface as PPOTrainer/ImpalaTrainer."""
 
@@ -245,6 +357,10 @@ class DQNTrainer(ImpalaTrainer):
         if cfg.learner not in LEARNERS:
             raise ValueError("DQNConfig.learner must be 'torch' or "
                              f"'device', not {cfg.learner!r}")
+        if cfg.head_step == "fused" and not getattr(policy, "_fused_head_ok",
+                                                    False):
+            raise ValueError("DQNConfig.head_step='fused' serves the fused "
+                             "head shapes only (policy._fused_head_ok)")
         super().__init__(vector_env, policy, None, device=device)
         self.config = cfg
         self.optimizer = torch.optim.Adam(self.policy.parameters(),
@@ -361,6 +477,32 @@ class DQNTrainer(ImpalaTrainer):
         return (loss, torch.stack([st[k] for k in STAT_KEYS]),
                 st["td_abs"].double())
 
+    def _head_step(self, idx, target_emb, err, weights=None):
+        """``_loss_device`` of the ring rows ``idx`` with
+        ``head_step="fused"``: the kernels on a GPU (``err`` collects their
+        validation flag), ``dqn_head_step_reference`` on CPU tensors."""
+        from ..models.gnn import graph_mean
+        from .device_actor import head_params
+        cfg = self.config
+        mb_static = self.env._models_batch
+        model_emb = graph_mean(self.policy.gnn(mb_static), mb_static)
+        ring = self.replay_dev.ring()
+        args = (cfg.v_min, cfg.v_max, cfg.dueling, cfg.double_q)
+        if model_emb.is_cuda:
+            return _DQNHeadStepFn.apply(
+                ring, idx, model_emb, target_emb, head_params(self.target),
+                *args, weights, err, *head_tensors(self.policy))
+        return dqn_head_step_reference(
+            ring, idx, model_emb, target_emb, head_tensors(self.policy),
+            head_params(self.target), *args, weights=weights)
+
+    def _check_head_step(self, flag: float):
+        """``flag``: the kernels' validation flag, read with the stats."""
+        if flag != 0:
+            raise RuntimeError(
+                "dqn_head_step: a minibatch named a ring slot, a model id or "
+                "an action out of range")
+
     def _update_device(self, data: Dict) -> Dict[str, float]:
         from ..models.gnn import graph_mean
         cfg = self.config
@@ -377,6 +519,7 @@ class DQNTrainer(ImpalaTrainer):
         if cfg.prioritized_replay:
             return self._update_device_prioritized(data)
         stats = {k: 0.0 for k in STAT_KEYS}
+        fused = cfg.head_step == "fused"
         if len(replay) >= cfg.learning_starts and cfg.num_sgd_iter > 0:
             rng = np.random.RandomState(self.iteration)
             # the torch learner's draws, uploaded once
@@ -389,9 +532,14 @@ class DQNTrainer(ImpalaTrainer):
                 mb_static = self.env._models_batch
                 target_emb = graph_mean(self.target.gnn(mb_static), mb_static)
             acc = torch.zeros(len(STAT_KEYS), device=replay.device)
+            err = (torch.zeros(1, dtype=torch.int32, device=replay.device)
+                   if fused and replay.device.type == "cuda" else None)
             for k in range(cfg.num_sgd_iter):
-                loss, stats_t = self._loss_device(replay.gather(idx[k]),
-                                                  target_emb)
+                if fused:
+                    loss, stats_t = self._head_step(idx[k], target_emb, err)
+                else:
+                    loss, stats_t = self._loss_device(replay.gather(idx[k]),
+                                                      target_emb)
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
                 all_reduce_gradients(self.policy.parameters())
@@ -401,9 +549,16 @@ class DQNTrainer(ImpalaTrainer):
                 self.optimizer.step()
                 acc += stats_t.detach()
             # one D2H for all stats of all minibatches
-            stats = dict(zip(STAT_KEYS, (acc / cfg.num_sgd_iter).tolist()))
+            acc = acc / cfg.num_sgd_iter
+            if err is not None:
+                acc = torch.cat([acc, err.float()])
+            out = acc.tolist()
+            if err is not None:
+                self._check_head_step(out[len(STAT_KEYS)])
+            stats = dict(zip(STAT_KEYS, out))
         stats["replay"] = len(replay)
         stats["learner"] = 1
+        stats["head_step"] = int(fused and replay.device.type == "cuda")
         self._sync_target(data)
         return stats
 
@@ -417,6 +572,7 @@ class DQNTrainer(ImpalaTrainer):
         replay = self.replay_dev
         keys = STAT_KEYS + PER_STAT_KEYS
         stats = {k: 0.0 for k in keys}
+        fused = cfg.head_step == "fused"
         if len(replay) >= cfg.learning_starts and cfg.num_sgd_iter > 0:
             rng = np.random.RandomState(self.iteration)
             # the torch learner's uniforms, uploaded once
@@ -427,10 +583,16 @@ class DQNTrainer(ImpalaTrainer):
                 mb_static = self.env._models_batch
                 target_emb = graph_mean(self.target.gnn(mb_static), mb_static)
             acc = torch.zeros(len(STAT_KEYS) + 1, device=replay.device)
+            err = (torch.zeros(1, dtype=torch.int32, device=replay.device)
+                   if fused and replay.device.type == "cuda" else None)
             for k in range(cfg.num_sgd_iter):
                 idx, weight = replay.sample(u[k])
-                loss, stats_t, td_abs = self._loss_device(
-                    replay.gather(idx), target_emb, weights=weight)
+                if fused:
+                    loss, stats_t, td_abs = self._head_step(
+                        idx, target_emb, err, weights=weight)
+                else:
+                    loss, stats_t, td_abs = self._loss_device(
+                        replay.gather(idx), target_emb, weights=weight)
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
                 all_reduce_gradients(self.policy.parameters())
@@ -442,11 +604,16 @@ class DQNTrainer(ImpalaTrainer):
                 acc[:len(STAT_KEYS)] += stats_t.detach()
                 acc[len(STAT_KEYS)] += weight.mean()
             # one D2H for all stats of all minibatches and max_prio
-            out = torch.cat([acc.double() / cfg.num_sgd_iter,
-                             replay.max_prio])
-            stats = dict(zip(keys, out.tolist()))
+            parts = [acc.double() / cfg.num_sgd_iter, replay.max_prio]
+            if err is not None:
+                parts.append(err.double())
+            out = torch.cat(parts).tolist()
+            if err is not None:
+                self._check_head_step(out[len(keys)])
+            stats = dict(zip(keys, out))
         stats["replay"] = len(replay)
         stats["learner"] = 1
+        stats["head_step"] = int(fused and replay.device.type == "cuda")
         self._sync_target(data)
         return stats
 

@@ -214,6 +214,7 @@ def build_trainer_from_config(cfg: dict, device=None):
             sgd_minibatch_size=algo.get("sgd_minibatch_size", 256),
             num_sgd_iter=algo.get("num_sgd_iter", 4),
             learner=str(algo.get("learner", "torch")),
+            head_step=str(algo.get("head_step", "torch")),
             prioritized_replay=bool(algo.get("prioritized_replay", False)),
             prioritized_replay_alpha=algo.get(
                 "prioritized_replay_alpha", 0.9),

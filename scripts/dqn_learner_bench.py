@@ -26,8 +26,15 @@ launch count then also reports the ``per_`` kernels, expected to be
 one ``per_sample_kernel`` and one ``per_update_kernel``): 9 at the yaml's
 num_sgd_iter = 4.
 
+``--head-step fused`` gives the device learner the fused Q-head step
+(ops/hip/dqn_head_step.hip) and adds a third trainer, ``device_torch_head``
+(the device learner with the torch head step), to the alternation, so the
+two head steps are timed in the same process; the launch count is that of
+the ``device`` trainer.
+
 Usage: python scripts/dqn_learner_bench.py [--envs 256] [--iters 10]
-           [--warmup 2] [--prioritized] [--count-launches] [--out FILE]
+           [--warmup 2] [--prioritized] [--head-step {torch,fused}]
+           [--count-launches] [--out FILE]
 """
 import argparse
 import json
@@ -59,6 +66,8 @@ def main():
                     help="untimed iterations per learner")
     ap.add_argument("--prioritized", action="store_true",
                     help="prioritized replay in both learners")
+    ap.add_argument("--head-step", choices=("torch", "fused"),
+                    default="torch", help="the device learner's Q-head step")
     ap.add_argument("--count-launches", action="store_true")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
@@ -89,7 +98,7 @@ def main():
     num_actions = cfg["env_config"].get("max_partitions_per_op", 16) + 1
     steps = max(1, algo["train_batch_size"] // args.envs)
 
-    def trainer(learner):
+    def trainer(learner, head_step="torch"):
         venv = EngineVectorEnv(env_fn, num_envs=args.envs, device=dev,
                                base_seed=0, spec=spec, proto_env=proto)
         torch.manual_seed(0)
@@ -102,13 +111,17 @@ def main():
             train_batch_size=algo["train_batch_size"],
             sgd_minibatch_size=algo["sgd_minibatch_size"],
             num_sgd_iter=algo["num_sgd_iter"], learner=learner,
+            head_step=head_step,
             prioritized_replay=args.prioritized,
             prioritized_replay_alpha=algo["prioritized_replay_alpha"],
             prioritized_replay_beta=algo["prioritized_replay_beta"],
             prioritized_replay_eps=algo["prioritized_replay_eps"]),
             device=dev)
 
-    trainers = {"torch": trainer("torch"), "device": trainer("device")}
+    trainers = {"torch": trainer("torch"),
+                "device": trainer("device", args.head_step)}
+    if args.head_step == "fused":
+        trainers["device_torch_head"] = trainer("device")
     sync = torch.cuda.synchronize
 
     def iteration(name):
@@ -140,9 +153,11 @@ def main():
            "sgd_minibatch_size": algo["sgd_minibatch_size"],
            "num_sgd_iter": algo["num_sgd_iter"], "n_step": algo["n_step"],
            "iters": args.iters, "warmup": args.warmup,
-           "prioritized": args.prioritized}
+           "prioritized": args.prioritized, "head_step": args.head_step}
     for name in trainers:
-        assert last[name]["learner"] == (1 if name == "device" else 0)
+        assert last[name]["learner"] == (0 if name == "torch" else 1)
+        assert last[name].get("head_step", 0) == int(
+            name == "device" and args.head_step == "fused")
         assert last[name]["total_loss"] > 0, "the timed updates must train"
         out[name] = {"update_time_s": summary(update[name]),
                      "rollout_time_s": summary(rollout[name]),
@@ -154,6 +169,10 @@ def main():
     out["update_time_ratio_torch_over_device"] = (
         out["torch"]["update_time_s"]["mean"]
         / out["device"]["update_time_s"]["mean"])
+    if args.head_step == "fused":
+        out["update_time_ratio_torch_head_over_fused"] = (
+            out["device_torch_head"]["update_time_s"]["mean"]
+            / out["device"]["update_time_s"]["mean"])
     out["rollout_time_ratio_torch_over_device"] = (
         out["torch"]["rollout_time_s"]["mean"]
         / out["device"]["rollout_time_s"]["mean"])
@@ -190,6 +209,7 @@ def main():
     out["device_update_launches"] = {
         "kernels": len(names),
         "dqn_kernels": sum(n.startswith("dqn_") for n in names),
+        "dqn_hs_kernels": sum(n.startswith("dqn_hs_") for n in names),
         # less the ingest (and, prioritized, the per_ingest) launch
         "per_minibatch": (len(names) - (2 if args.prioritized else 1))
         / algo["num_sgd_iter"]}
