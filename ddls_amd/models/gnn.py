@@ -65,6 +65,7 @@ class GraphBatch:
     num_graphs: int
     _csr: Optional[tuple] = None
     _node_ptr: Optional[torch.Tensor] = None
+    _trunk: Optional[tuple] = None
 
     def csr_by_dst(self):
         """(edge_order, indptr) with edges sorted by destination node —
@@ -89,6 +90,45 @@ class GraphBatch:
             torch.cumsum(counts, 0, out=ptr[1:])
             self._node_ptr = ptr
         return self._node_ptr
+
+    def trunk_plan(self):
+        """The int32 index plan of the gnn_trunk kernels, built and validated
+        on the host once (one sync; the batch is static): ``(eo, srcp, dstp,
+        indptr, sptr, slist, node_ptr)``.  ``eo`` is the stable CSR-by-dst
+        edge order of ``csr_by_dst()`` and ``indptr`` its row pointer;
+        ``srcp`` / ``dstp`` are ``src`` / ``dst`` in that order; ``sptr`` /
+        ``slist`` are a CSR by source over the positions of that order."""
+        if self._trunk is None:
+            n, E, G = self.z.shape[0], self.src.shape[0], self.num_graphs
+            src = self.src.detach().cpu().numpy().astype(np.int64)
+            dst = self.dst.detach().cpu().numpy().astype(np.int64)
+            gon = self.graph_of_node.detach().cpu().numpy().astype(np.int64)
+            if n < 1 or G < 1 or gon.shape[0] != n or self.e.shape[0] != E:
+                raise ValueError("gnn_trunk: the batch needs nodes, graphs "
+                                 "and one feature row per node and edge")
+            if gon.min() < 0 or gon.max() >= G or np.any(np.diff(gon) < 0):
+                raise ValueError("gnn_trunk: nodes must be stored "
+                                 "graph-contiguously with ids in [0, G)")
+            if E and (min(src.min(), dst.min()) < 0
+                      or max(src.max(), dst.max()) >= n):
+                raise ValueError("gnn_trunk: an edge names a node outside "
+                                 "[0, N)")
+            if np.any(gon[src] != gon[dst]):
+                raise ValueError("gnn_trunk: an edge joins two graphs")
+            eo = np.argsort(dst, kind="stable")
+            srcp, dstp = src[eo], dst[eo]
+            slist = np.argsort(srcp, kind="stable")
+
+            def ptr(ids, size):
+                out = np.zeros(size + 1, dtype=np.int64)
+                np.cumsum(np.bincount(ids, minlength=size), out=out[1:])
+                return out
+            plan = (eo, srcp, dstp, ptr(dst, n), ptr(src, n), slist,
+                    ptr(gon, G))
+            self._trunk = tuple(
+                torch.as_tensor(a.astype(np.int32), device=self.z.device)
+                for a in plan)
+        return self._trunk
 
     @staticmethod
     def from_padded(node_features: torch.Tensor,
@@ -313,6 +353,17 @@ class GNN(nn.Module):
                                     config["module_depth"]))
         self.layers = nn.ModuleList(layers)
 
+        # gnn_trunk eligibility (ops/hip/gnn_trunk.hip is built for the tuned
+        # PAC-ML GNN shape)
+        self._trunk_ok = (
+            config["num_rounds"] == 2 and config["module_depth"] == 1
+            and config["aggregator_activation"] == "relu"
+            and config["in_features_node"] == 5
+            and config["in_features_edge"] == 2
+            and config["out_features_msg"] == 32
+            and config["out_features_hidden"] == 64
+            and config["out_features_node"] == 16)
+
     def forward(self, batch: GraphBatch) -> torch.Tensor:
         z = batch.z
         for layer in self.layers:
@@ -399,6 +450,45 @@ def graph_mean(node_emb: torch.Tensor, batch: GraphBatch) -> torch.Tensor:
     counts.index_add_(0, batch.graph_of_node,
                       torch.ones_like(batch.graph_of_node, dtype=node_emb.dtype))
     return sums / counts.clamp(min=1).unsqueeze(-1)
+
+
+class _GNNTrunkFn(torch.autograd.Function):
+    """The whole GNN trunk, ``graph_mean(gnn(batch), batch)``, as the kernels
+    of ops/hip/gnn_trunk.hip: one launch forward, two backward.  Inputs are
+    the batch (a constant: ``z`` and ``e`` get no gradient) and the 24
+    tensors of ``gnn.parameters()``; the output is ``[G, 16]``."""
+
+    @staticmethod
+    def forward(ctx, batch, *params):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        plan = list(batch.trunk_plan())
+        params_c = [p.detach().contiguous() for p in params]
+        emb, workspace = ext.gnn_trunk_fwd(
+            batch.z.detach().contiguous(), batch.e.detach().contiguous(),
+            plan, params_c)
+        ctx.save_for_backward(workspace, *plan, *params_c)
+        return emb
+
+    @staticmethod
+    def backward(ctx, gemb):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        saved = ctx.saved_tensors
+        grads = ext.gnn_trunk_bwd(gemb.contiguous(), saved[0],
+                                  list(saved[1:8]), list(saved[8:]))
+        return (None,) + tuple(grads)
+
+
+def gnn_trunk(gnn: GNN, batch: GraphBatch) -> torch.Tensor:
+    """Per-graph mean node embedding ``[G, out_node]`` of ``gnn`` on
+    ``batch``.  An eligible GNN (``gnn._trunk_ok``) on a GPU runs the fused
+    trunk kernels, forward and backward; anything else is the torch chain
+    ``graph_mean(gnn(batch), batch)``, which is also the kernels' oracle."""
+    if (getattr(gnn, "_trunk_ok", False) and batch.z.is_cuda
+            and os.environ.get("DDLS_AMD_DISABLE_HIP", "0") != "1"):
+        return _GNNTrunkFn.apply(batch, *gnn.parameters())
+    return graph_mean(gnn(batch), batch)
 
 
 class GNNPolicy(nn.Module):

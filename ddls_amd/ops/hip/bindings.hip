@@ -118,6 +118,13 @@ std::vector<torch::Tensor> dqn_head_step_fwd(
 std::vector<torch::Tensor> dqn_head_step_bwd(
     std::vector<torch::Tensor> saved, std::vector<torch::Tensor> online,
     torch::Tensor gl, int64_t M, bool dueling);
+std::vector<torch::Tensor> gnn_trunk_fwd(torch::Tensor z, torch::Tensor e,
+                                         std::vector<torch::Tensor> plan,
+                                         std::vector<torch::Tensor> params);
+std::vector<torch::Tensor> gnn_trunk_bwd(torch::Tensor gemb,
+                                         torch::Tensor workspace,
+                                         std::vector<torch::Tensor> plan,
+                                         std::vector<torch::Tensor> params);
 void per_ingest(torch::Tensor tree_sum, torch::Tensor tree_min,
                 torch::Tensor max_prio, int64_t start, int64_t count,
                 int64_t capacity, double alpha);
@@ -215,6 +222,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("dqn_head_step_bwd", &dqn_head_step_bwd,
           "analytic backward of dqn_head_step_fwd into the online head "
           "tensors and model_emb (MFMA weight-grad tiles)");
+    m.def("gnn_trunk_fwd", &gnn_trunk_fwd,
+          "GNN trunk forward (two MeanPool rounds + graph mean) in one "
+          "launch, one workgroup per graph; returns model_emb and the "
+          "workspace the backward reads");
+    m.def("gnn_trunk_bwd", &gnn_trunk_bwd,
+          "analytic GNN trunk backward into the 24 gnn.parameters() tensors "
+          "(row kernel + MFMA weight-grad tiles)");
     m.def("per_ingest", &per_ingest,
           "prioritized replay: new slots enter the sum/min trees at "
           "max_prio^alpha");

@@ -41,6 +41,12 @@ the three head passes, the loss and their autograd backward by the kernels of
 ``ops/hip/dqn_head_step.hip``: three launches forward and two backward per
 minibatch, reading the ring through the minibatch's slot indices.  The GNN
 forward and backward and the optimizer stay as they are.
+
+``DQNConfig.trunk_step="fused"`` (device learner only) replaces that GNN
+forward and its autograd backward, ``graph_mean(policy.gnn(models_batch))``,
+by the kernels of ``ops/hip/gnn_trunk.hip`` (``models.gnn.gnn_trunk``): one
+launch forward and two backward per minibatch, and one forward per update for
+the target net.  It combines with either ``head_step``.
 """
 from __future__ import annotations
 
@@ -58,6 +64,7 @@ from .rollout import CompactObs
 
 
 HEAD_STEPS = ("torch", "fused")
+TRUNK_STEPS = ("torch", "fused")
 
 
 @dataclass
@@ -91,8 +98,15 @@ class DQNConfig:
     # passes + the fused loss.  "fused": the kernels of
     # ops/hip/dqn_head_step.hip (policy._fused_head_ok shapes only)
     head_step: str = "torch"
+    # the device learner's GNN trunk.  "torch": graph_mean(gnn(batch)) as
+    # per-layer kernels under autograd.  "fused": the kernels of
+    # ops/hip/gnn_trunk.hip (policy.gnn._trunk_ok shapes only)
+    trunk_step: str = "torch"
 
     def __post_init__(self):
+        if self.trunk_step not in TRUNK_STEPS:
+            raise ValueError("DQNConfig.trunk_step must be 'torch' or "
+                             f"'fused', not {self.trunk_step!r}")
         if self.head_step not in HEAD_STEPS:
             raise ValueError("DQNConfig.head_step must be 'torch' or "
                              f"'fused', not {self.head_step!r}")
@@ -361,6 +375,10 @@ class DQNTrainer(ImpalaTrainer):
                                                     False):
             raise ValueError("DQNConfig.head_step='fused' serves the fused "
                              "head shapes only (policy._fused_head_ok)")
+        if cfg.trunk_step == "fused" and not getattr(
+                getattr(policy, "gnn", None), "_trunk_ok", False):
+            raise ValueError("DQNConfig.trunk_step='fused' serves the tuned "
+                             "GNN shape only (policy.gnn._trunk_ok)")
         super().__init__(vector_env, policy, None, device=device)
         self.config = cfg
         self.optimizer = torch.optim.Adam(self.policy.parameters(),
@@ -445,15 +463,26 @@ class DQNTrainer(ImpalaTrainer):
                 torch.log(gfull[:, 17:]), min=torch.finfo(torch.float32).min)
         return logits, values
 
+    def _model_emb(self, net):
+        """``net``'s per-model GNN embeddings of the static models batch."""
+        from ..models.gnn import gnn_trunk, graph_mean
+        mb_static = self.env._models_batch
+        if self.config.trunk_step == "fused":
+            return gnn_trunk(net.gnn, mb_static)
+        return graph_mean(net.gnn(mb_static), mb_static)
+
+    def _trunk_stat(self) -> int:
+        """1 when the trunk kernels serve this learner's updates."""
+        return int(self.config.trunk_step == "fused"
+                   and self.replay_dev.device.type == "cuda")
+
     def _loss_device(self, mb: Dict, target_emb, weights=None):
         """(loss, stats[4] tensor in STAT_KEYS order) of one ring minibatch:
         the fused kernels on a GPU, the torch chain on CPU tensors (the
         CpuEngine backend).  With importance ``weights`` the loss is weighted
         and a third value is the rows' unweighted |td| in f64."""
-        from ..models.gnn import graph_mean
         cfg = self.config
-        mb_static = self.env._models_batch
-        model_emb = graph_mean(self.policy.gnn(mb_static), mb_static)
+        model_emb = self._model_emb(self.policy)
         logits_s, values_s = self._heads(self.policy, model_emb,
                                          mb["s_gfull"], mb["s_model"])
         with torch.no_grad():
@@ -481,11 +510,9 @@ class DQNTrainer(ImpalaTrainer):
         """``_loss_device`` of the ring rows ``idx`` with
         ``head_step="fused"``: the kernels on a GPU (``err`` collects their
         validation flag), ``dqn_head_step_reference`` on CPU tensors."""
-        from ..models.gnn import graph_mean
         from .device_actor import head_params
         cfg = self.config
-        mb_static = self.env._models_batch
-        model_emb = graph_mean(self.policy.gnn(mb_static), mb_static)
+        model_emb = self._model_emb(self.policy)
         ring = self.replay_dev.ring()
         args = (cfg.v_min, cfg.v_max, cfg.dueling, cfg.double_q)
         if model_emb.is_cuda:
@@ -504,7 +531,6 @@ class DQNTrainer(ImpalaTrainer):
                 "an action out of range")
 
     def _update_device(self, data: Dict) -> Dict[str, float]:
-        from ..models.gnn import graph_mean
         cfg = self.config
         if self.replay_dev is None:
             self.replay_dev = DeviceReplay(
@@ -529,8 +555,7 @@ class DQNTrainer(ImpalaTrainer):
                           for _ in range(cfg.num_sgd_iter)]),
                 device=replay.device)
             with torch.no_grad():
-                mb_static = self.env._models_batch
-                target_emb = graph_mean(self.target.gnn(mb_static), mb_static)
+                target_emb = self._model_emb(self.target)
             acc = torch.zeros(len(STAT_KEYS), device=replay.device)
             err = (torch.zeros(1, dtype=torch.int32, device=replay.device)
                    if fused and replay.device.type == "cuda" else None)
@@ -559,6 +584,7 @@ class DQNTrainer(ImpalaTrainer):
         stats["replay"] = len(replay)
         stats["learner"] = 1
         stats["head_step"] = int(fused and replay.device.type == "cuda")
+        stats["trunk_step"] = self._trunk_stat()
         self._sync_target(data)
         return stats
 
@@ -567,7 +593,6 @@ class DQNTrainer(ImpalaTrainer):
         per minibatch sample -> gather -> weighted loss -> step ->
         update_priorities, all on the ring's device, and still one D2H per
         update."""
-        from ..models.gnn import graph_mean
         cfg = self.config
         replay = self.replay_dev
         keys = STAT_KEYS + PER_STAT_KEYS
@@ -580,8 +605,7 @@ class DQNTrainer(ImpalaTrainer):
                 rng.random_sample((cfg.num_sgd_iter, cfg.sgd_minibatch_size)),
                 device=replay.device)
             with torch.no_grad():
-                mb_static = self.env._models_batch
-                target_emb = graph_mean(self.target.gnn(mb_static), mb_static)
+                target_emb = self._model_emb(self.target)
             acc = torch.zeros(len(STAT_KEYS) + 1, device=replay.device)
             err = (torch.zeros(1, dtype=torch.int32, device=replay.device)
                    if fused and replay.device.type == "cuda" else None)
@@ -614,6 +638,7 @@ class DQNTrainer(ImpalaTrainer):
         stats["replay"] = len(replay)
         stats["learner"] = 1
         stats["head_step"] = int(fused and replay.device.type == "cuda")
+        stats["trunk_step"] = self._trunk_stat()
         self._sync_target(data)
         return stats
 

@@ -215,6 +215,7 @@ def build_trainer_from_config(cfg: dict, device=None):
             num_sgd_iter=algo.get("num_sgd_iter", 4),
             learner=str(algo.get("learner", "torch")),
             head_step=str(algo.get("head_step", "torch")),
+            trunk_step=str(algo.get("trunk_step", "torch")),
             prioritized_replay=bool(algo.get("prioritized_replay", False)),
             prioritized_replay_alpha=algo.get(
                 "prioritized_replay_alpha", 0.9),

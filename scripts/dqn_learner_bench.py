@@ -32,9 +32,14 @@ num_sgd_iter = 4.
 two head steps are timed in the same process; the launch count is that of
 the ``device`` trainer.
 
+``--trunk-step fused`` gives the device learner the fused GNN trunk
+(ops/hip/gnn_trunk.hip) with the same protocol: the third trainer is then
+``device_torch_trunk``, the device learner with the same ``--head-step`` and
+the torch trunk, and the launch count is taken for both of them.
+
 Usage: python scripts/dqn_learner_bench.py [--envs 256] [--iters 10]
            [--warmup 2] [--prioritized] [--head-step {torch,fused}]
-           [--count-launches] [--out FILE]
+           [--trunk-step {torch,fused}] [--count-launches] [--out FILE]
 """
 import argparse
 import json
@@ -68,6 +73,8 @@ def main():
                     help="prioritized replay in both learners")
     ap.add_argument("--head-step", choices=("torch", "fused"),
                     default="torch", help="the device learner's Q-head step")
+    ap.add_argument("--trunk-step", choices=("torch", "fused"),
+                    default="torch", help="the device learner's GNN trunk")
     ap.add_argument("--count-launches", action="store_true")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
@@ -98,7 +105,7 @@ def main():
     num_actions = cfg["env_config"].get("max_partitions_per_op", 16) + 1
     steps = max(1, algo["train_batch_size"] // args.envs)
 
-    def trainer(learner, head_step="torch"):
+    def trainer(learner, head_step="torch", trunk_step="torch"):
         venv = EngineVectorEnv(env_fn, num_envs=args.envs, device=dev,
                                base_seed=0, spec=spec, proto_env=proto)
         torch.manual_seed(0)
@@ -111,7 +118,7 @@ def main():
             train_batch_size=algo["train_batch_size"],
             sgd_minibatch_size=algo["sgd_minibatch_size"],
             num_sgd_iter=algo["num_sgd_iter"], learner=learner,
-            head_step=head_step,
+            head_step=head_step, trunk_step=trunk_step,
             prioritized_replay=args.prioritized,
             prioritized_replay_alpha=algo["prioritized_replay_alpha"],
             prioritized_replay_beta=algo["prioritized_replay_beta"],
@@ -119,8 +126,10 @@ def main():
             device=dev)
 
     trainers = {"torch": trainer("torch"),
-                "device": trainer("device", args.head_step)}
-    if args.head_step == "fused":
+                "device": trainer("device", args.head_step, args.trunk_step)}
+    if args.trunk_step == "fused":
+        trainers["device_torch_trunk"] = trainer("device", args.head_step)
+    elif args.head_step == "fused":
         trainers["device_torch_head"] = trainer("device")
     sync = torch.cuda.synchronize
 
@@ -153,11 +162,15 @@ def main():
            "sgd_minibatch_size": algo["sgd_minibatch_size"],
            "num_sgd_iter": algo["num_sgd_iter"], "n_step": algo["n_step"],
            "iters": args.iters, "warmup": args.warmup,
-           "prioritized": args.prioritized, "head_step": args.head_step}
+           "prioritized": args.prioritized, "head_step": args.head_step,
+           "trunk_step": args.trunk_step}
     for name in trainers:
         assert last[name]["learner"] == (0 if name == "torch" else 1)
         assert last[name].get("head_step", 0) == int(
-            name == "device" and args.head_step == "fused")
+            name in ("device", "device_torch_trunk")
+            and args.head_step == "fused")
+        assert last[name].get("trunk_step", 0) == int(
+            name == "device" and args.trunk_step == "fused")
         assert last[name]["total_loss"] > 0, "the timed updates must train"
         out[name] = {"update_time_s": summary(update[name]),
                      "rollout_time_s": summary(rollout[name]),
@@ -169,7 +182,11 @@ def main():
     out["update_time_ratio_torch_over_device"] = (
         out["torch"]["update_time_s"]["mean"]
         / out["device"]["update_time_s"]["mean"])
-    if args.head_step == "fused":
+    if args.trunk_step == "fused":
+        out["update_time_ratio_torch_trunk_over_fused"] = (
+            out["device_torch_trunk"]["update_time_s"]["mean"]
+            / out["device"]["update_time_s"]["mean"])
+    elif args.head_step == "fused":
         out["update_time_ratio_torch_head_over_fused"] = (
             out["device_torch_head"]["update_time_s"]["mean"]
             / out["device"]["update_time_s"]["mean"])
@@ -195,29 +212,36 @@ def main():
     # kernels launched by one device update(), the ingest included
     from torch.autograd import DeviceType
     from torch.profiler import ProfilerActivity, profile
-    tr = trainers["device"]
-    data = tr.collect_rollout(steps)
-    sync()
-    with profile(activities=[ProfilerActivity.CPU,
-                             ProfilerActivity.CUDA]) as prof:
-        tr.update(data)
+
+    def count(name):
+        tr = trainers[name]
+        data = tr.collect_rollout(steps)
         sync()
-    tr.iteration += 1
-    names = [e.name for e in prof.events()
-             if e.device_type == DeviceType.CUDA
-             and not e.name.lower().startswith(("memcpy", "memset"))]
-    out["device_update_launches"] = {
-        "kernels": len(names),
-        "dqn_kernels": sum(n.startswith("dqn_") for n in names),
-        "dqn_hs_kernels": sum(n.startswith("dqn_hs_") for n in names),
-        # less the ingest (and, prioritized, the per_ingest) launch
-        "per_minibatch": (len(names) - (2 if args.prioritized else 1))
-        / algo["num_sgd_iter"]}
-    if args.prioritized:
-        out["device_update_launches"]["per_kernels"] = sum(
-            n.startswith("per_") for n in names)
-        out["device_update_launches"]["per_kernels_expected"] = \
-            1 + 2 * algo["num_sgd_iter"]
+        with profile(activities=[ProfilerActivity.CPU,
+                                 ProfilerActivity.CUDA]) as prof:
+            tr.update(data)
+            sync()
+        tr.iteration += 1
+        names = [e.name for e in prof.events()
+                 if e.device_type == DeviceType.CUDA
+                 and not e.name.lower().startswith(("memcpy", "memset"))]
+        res = {
+            "kernels": len(names),
+            "dqn_kernels": sum(n.startswith("dqn_") for n in names),
+            "dqn_hs_kernels": sum(n.startswith("dqn_hs_") for n in names),
+            "gt_kernels": sum(n.startswith("gt_") for n in names),
+            # less the ingest (and, prioritized, the per_ingest) launch
+            "per_minibatch": (len(names) - (2 if args.prioritized else 1))
+            / algo["num_sgd_iter"]}
+        if args.prioritized:
+            res["per_kernels"] = sum(n.startswith("per_") for n in names)
+            res["per_kernels_expected"] = 1 + 2 * algo["num_sgd_iter"]
+        return res
+
+    out["device_update_launches"] = count("device")
+    if args.trunk_step == "fused":
+        out["device_torch_trunk_update_launches"] = count(
+            "device_torch_trunk")
     emit()
 
 
