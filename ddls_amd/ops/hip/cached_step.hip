@@ -4,61 +4,60 @@
 // M <= 16 distinct workload-model graphs (~200 nodes total): the whole
 // fwd+bwd is ~10 MFLOP.  Run as torch autograd it is ~146 dispatches per
 // replay (42% zero-fill / grad-accumulate glue — profiles/
-// kernel_stats_r02_cachedsgd.csv); here it is SIX kernels (3 fwd + 3 bwd)
-// sized to the work's parallelism, with every weight gradient computed as a
-// deterministic LDS-tiled A^T.B contraction (no atomics, replay-stable):
+// kernel_stats_r02_cachedsgd.csv).  Here every weight gradient is a
+// deterministic LDS-tiled A^T.B contraction (no atomics, replay-stable) and
+// the step is one of two launch sequences, selected per call with
+// DDLS_AMD_STEP_PATH.  Both write every tensor of the C_* list below, in the
+// same bits (tests/test_step_paths.py).
 //
-//   fwd:  cs_fwd_gnn   (1 WG)   GNN rounds + pooling + per-sample `final`
-//         cs_fwd_head  (many)   FC branches over B x FC units
-//         cs_fwd_loss  (1 WG)   softmax/surrogate rows + device stats
-//   bwd:  cs_bwd_head  (many)   per-sample chain: glogits -> gh1 -> gfinal
-//         cs_bwd_gnn   (1 WG)   pool grads + both MeanPool rounds' data bwd
-//         cs_bwd_w     (many)   ALL weight/bias/LN grads into flat_g
+// production (default): 10 launches with the reduce deferred, 12 per replay
+// with the two-launch optimiser tail.  Rows of the GNN are lane-parallel (a
+// group of L lanes per row), neighbouring kernels with row-local or
+// sample-local dependencies are one launch, and work that waits for nothing
+// ahead of it rides as extra blocks of a launch that exists anyway:
 //
-// That was the first cut.  The step is now 13 launches (16 per replay with
-// the stage kernel and the two-launch optimiser tail), in this order:
-//
-//   fwd:  cs_fwd_mlp_lanes<1>        round-1 node / edge modules
-//         cs_fwd_reduce_lanes<1>     round-1 reduce module (edge + self rows)
+//   fwd:  cs_fwd_stage_mlp1_red1_lanes  block 0 gathers the minibatch from the
+//                                    device batch store (cs_stage.h); the
+//                                    rest: round-1 node / edge modules +
+//                                    round-1 reduce module (edge + self rows)
 //         cs_fwd_comb1_mlp2_lanes    h1 = CSR mean, then the round-2 modules
 //         cs_fwd_reduce_lanes<2>     round-2 reduce module
 //         cs_fwd_comb2_pool          h2 = CSR mean + per-model means
-//         cs_head                    per SAMPLE: final row, FC branches,
+//         cs_head2                   per SAMPLE: final row, FC branches,
 //                                    logits/value, loss row, and the whole
 //                                    head backward down to gfinal / gu34
-//   bwd:  cs_bwd_pool                pool grads -> gh2
+//   bwd:  cs_bwd_pool_wfc2           pool grads -> gh2, one block per model,
+//                                    beside the graph-module and FC-column
+//                                    (B-row) weight-grad blocks
 //         cs_bwd_reduce_lanes<2>     round-2 reduce module backward
 //         cs_bwd_scat2_mlp2_lanes    scatter to ghn2/ghe2 + round-2 modules
 //         cs_bwd_reduce_lanes<1>     round-1 reduce module backward
-//         cs_bwd_scat1_gu1           scatter to ghn1/ghe1 + module-1 gu rows
-//                                    (+ one block for the C_STATS sums)
-//         cs_bwd_w, cs_bwd_w_reduce  all weight grads into flat_g
+//         cs_bwd_scat1_gu1_w         scatter to ghn1/ghe1 + module-1 gu rows
+//                                    (+ one block for the C_STATS sums) and
+//                                    the 6 x WSPLIT row-split weight-grad jobs
+//         cs_bwd_w_reduce            the row jobs' partial sums into flat_g,
+//                                    unless the caller defers them to the
+//                                    folded optimiser tail
+//   With DDLS_AMD_WGRAD_MFMA=1 the row jobs are not split, and the last
+//   launches are cs_bwd_scat1_gu1 + cs_bwd_w (six blocks, no reduce).
 //
-// By default two of those carry work that waits for nothing ahead of it in
-// the chain (section "work off the serial chain" below): the first forward
-// launch is cs_fwd_stage_mlp1_lanes (block 0 gathers the minibatch, so the
-// stage kernel's own launch goes away: 15 per replay), and cs_bwd_pool is
-// cs_bwd_pool_wfc, one pool block per model beside the 17 B-row weight-grad
-// blocks that cs_bwd_w then no longer launches.  DDLS_AMD_STEP_OVERLAP=off
-// launches the sequence above.
+// reference (DDLS_AMD_STEP_PATH=reference): 20 launches, the oldest and
+// plainest code: one thread per row, every stage a kernel of its own.  It is
+// what tests/test_cached_step_shapes.py pins to torch autograd, and the
+// production path is pinned to it bit for bit.
 //
-// By default three pairs of those are merged along row-local dependencies
-// (DDLS_AMD_STEP_MERGE, sections "cs_stage + round-1 node / edge modules +
-// round-1 reduce module" and "cs_bwd_scat1_gu1 + the row jobs of cs_bwd_w"
-// below): the first two forward launches are one, cs_bwd_scat1_gu1 and
-// cs_bwd_w are one, and cs_bwd_w_reduce's sums are formed by the first
-// kernel of the optimiser tail when the caller defers them: 12 per replay.
+//   fwd:  cs_fwd_mlp<1>, cs_fwd_reduce<1>, cs_fwd_combine<1>,
+//         cs_fwd_mlp<2>, cs_fwd_reduce<2>, cs_fwd_combine<2>,
+//         cs_fwd_pool, cs_fwd_head, cs_fwd_logits, cs_fwd_loss
+//   bwd:  cs_bwd_head, cs_bwd_pool,
+//         cs_bwd_reduce<2>, cs_bwd_scatter<2>, cs_bwd_mlp2,
+//         cs_bwd_reduce<1>, cs_bwd_scatter<1>, cs_bwd_gu1,
+//         cs_bwd_w (6 x nsplit row jobs + 17 B-row blocks), cs_bwd_w_reduce
 //
-// By default the two longest of those twelve run with shorter chains
-// (DDLS_AMD_STEP_HEAD, sections "cs_head with a shorter chain" and
-// "cs_bwd_pool_wfc with shorter roles" below): cs_head2 in place of cs_head
-// and cs_bwd_pool_wfc2 in place of cs_bwd_pool_wfc, the same launches with
-// the same outputs in the same bits.  DDLS_AMD_STEP_HEAD=off launches the
-// two kernels they replace.
-//
-// DDLS_AMD_STEP_FUSION=off launches the previous 20 separate kernels and
-// DDLS_AMD_ROW_KERNELS=thread the thread-per-row ones before them; both
-// sets stay in this file unchanged as oracles for bitwise comparison.
+// The production kernels were derived from the reference ones in steps, each
+// pinned bitwise to its predecessor; the comments below name the reference
+// kernel whose sums and roundings a production kernel reproduces.  The
+// intermediate launch sequences are history: docs/KERNELS.md.
 //
 // Exact-by-linearity gradient aggregation: per-sample dL/d emb reaches the
 // (shared) per-model GNN summed over the minibatch — the same contraction
@@ -1461,9 +1460,8 @@ cs_bwd_w_reduce_kernel(CachedPtrs P, CachedDims D) {
 // cs_bwd_mlp2, cs_bwd_gu1) put the N+E graph rows on two workgroups and run
 // each row's LayerNorm and Din x Dout GEMV as one thread's serial chain.  The
 // kernels below give each row a group of L lanes and a block 256/L rows, so
-// the same work spreads over (N+E)*L/256 workgroups.  They are the default;
-// DDLS_AMD_ROW_KERNELS=thread launches the thread-per-row kernels instead,
-// which stay in the file unchanged as the oracle for bitwise comparison.
+// the same work spreads over (N+E)*L/256 workgroups.  They are the
+// production path's; the thread-per-row kernels are the reference path's.
 //
 // No sum is re-associated: every output element is still accumulated by one
 // lane in the order the thread-per-row code uses (i ascending for a forward
@@ -1636,35 +1634,6 @@ __device__ __forceinline__ void rows_bwd_lanes(
 // are block-uniform.
 template <int ROUND, int L>
 __global__ void __launch_bounds__(ROW_NT)
-cs_fwd_mlp_lanes_kernel(CachedPtrs P, CachedDims D) {
-  constexpr int RPB = ROW_NT / L;
-  const int nbN = (D.N + RPB - 1) / RPB;
-  if ((int)blockIdx.x < nbN) {
-    const long r0 = (long)blockIdx.x * RPB;
-    if (ROUND == 1)
-      rows_fwd_lanes<KF0, KH, 1, L>(
-          P, W_LN_N1_W, r0, D.N,
-          [&](long v, int i) { return P.z0[v * KF0 + i]; },
-          P.xh_z1, P.rst_z1, P.hn1);
-    else
-      rows_fwd_lanes<KHID, KH, 0, L>(
-          P, W_LN_N2_W, r0, D.N,
-          [&](long v, int i) { return P.h1[v * KHID + i]; },
-          P.xh_h2, P.rst_h2, P.hn2);
-  } else {
-    const long r0 = (long)(blockIdx.x - nbN) * RPB;
-    auto ld = [&](long k, int i) { return P.e[k * KFE + i]; };
-    if (ROUND == 1)
-      rows_fwd_lanes<KFE, KH, 0, L>(P, W_LN_E1_W, r0, D.E, ld, P.xh_e1,
-                                    P.rst_e1, P.he1);
-    else
-      rows_fwd_lanes<KFE, KH, 0, L>(P, W_LN_E2_W, r0, D.E, ld, P.xh_e2,
-                                    P.rst_e2, P.he2);
-  }
-}
-
-template <int ROUND, int L>
-__global__ void __launch_bounds__(ROW_NT)
 cs_fwd_reduce_lanes_kernel(CachedPtrs P, CachedDims D) {
   constexpr int RPB = ROW_NT / L;
   constexpr int DO = (ROUND == 1) ? KHID : KOUT;
@@ -1738,67 +1707,14 @@ cs_bwd_reduce_lanes_kernel(CachedPtrs P, CachedDims D) {
   }
 }
 
-template <int L>
-__global__ void __launch_bounds__(ROW_NT)
-cs_bwd_mlp2_lanes_kernel(CachedPtrs P, CachedDims D) {
-  constexpr int RPB = ROW_NT / L;
-  const int nbN = (D.N + RPB - 1) / RPB;
-  if ((int)blockIdx.x < nbN) {
-    const long r0 = (long)blockIdx.x * RPB;
-    rows_bwd_lanes<KHID, KH, KH, 0, L, true>(
-        P, W_LN_N2_W, r0, D.N,
-        [&](long v, int o) { return P.ghn2[v * KH + o]; },
-        P.hn2, P.xh_h2, P.rst_h2, P.gpn1, P.gu_h2, P.gh1b);
-  } else {
-    const long r0 = (long)(blockIdx.x - nbN) * RPB;
-    rows_bwd_lanes<KFE, KH, KH, 0, L, false>(
-        P, W_LN_E2_W, r0, D.E,
-        [&](long k, int o) { return P.ghe2[k * KH + o]; },
-        P.he2, nullptr, nullptr, P.gpe1, P.gu_e2, nullptr);
-  }
-}
-
-// module-1 LN-out grad rows: one thread per gu element (all 16 terms fused)
-__global__ void __launch_bounds__(ROW_NT)
-cs_bwd_gu1_lanes_kernel(CachedPtrs P, CachedDims D) {
-  __shared__ float sWN[KH * KF0], sWE[KH * KFE];
-  const int tid = threadIdx.x;
-  for (int x = tid; x < KH * KF0; x += ROW_NT) sWN[x] = WP(W_N1_W)[x];
-  for (int x = tid; x < KH * KFE; x += ROW_NT) sWE[x] = WP(W_E1_W)[x];
-  __syncthreads();
-  const long nU = (long)D.N * KF0;
-  const long total = nU + (long)D.E * KFE;
-  const long u = (long)blockIdx.x * ROW_NT + tid;
-  if (u >= total) return;
-  if (u < nU) {
-    const long v = u / KF0;
-    const int i = (int)(u % KF0);
-    float acc = 0.f;
-#pragma unroll
-    for (int o = 0; o < KH; ++o)
-      acc = FMA(sWN[o * KF0 + i], P.ghn1[v * KH + o], acc);
-    P.gu_z1[u] = acc;
-  } else {
-    const long x = u - nU;
-    const long k = x / KFE;
-    const int i = (int)(x % KFE);
-    float acc = 0.f;
-#pragma unroll
-    for (int o = 0; o < KH; ++o)
-      acc = FMA(sWE[o * KFE + i], P.ghe1[k * KH + o], acc);
-    P.gu_e1[x] = acc;
-  }
-}
-
 // ===========================================================================
 // fused launches
 // ===========================================================================
 //
 // Neighbouring kernels whose dependencies are row-local or sample-local, run
 // as one launch each (a replay is a serial chain of launches, each near the
-// dispatch floor).  Default; DDLS_AMD_STEP_FUSION=off launches the separate
-// kernels above, which stay in the file unchanged as the oracle.  Every
-// tensor the separate kernels wrote is still written, in the same bits: the
+// dispatch floor).  Production path; the separate kernels above are the
+// reference path's.  Every tensor they write is written, in the same bits: the
 // summation orders are theirs, and the roundings are the ones their gfx950
 // ISA has (docs/KERNELS.md "Round 6"):
 //   fwd_head       bias first, i = 0..23, every term fused
@@ -1810,7 +1726,6 @@ cs_bwd_gu1_lanes_kernel(CachedPtrs P, CachedDims D) {
 //   scatter        plain adds in src-CSR order
 
 // ---- per-sample chain: fwd_head + fwd_logits + fwd_loss + bwd_head ----
-#define HD_HS 4                    // samples in flight per block
 #define HD_CS 20                   // LDS stride of a 16-float chunk: lanes
                                    // that read one chunk each (b128) spread
                                    // over all banks
@@ -1819,313 +1734,29 @@ __device__ __forceinline__ int hd_pad(int j) {
   return (j >> 4) * HD_CS + (j & 15);
 }
 
-// Blocks and sample ranges are cs_bwd_head_kernel's: min(B, 32) blocks, each
-// walking its contiguous range HD_HS samples at a time.  Thread j owns hidden
-// unit j of both branches through the forward AND the backward (its W1p/W1v
-// rows sit in registers for the forward; h1p/h1v stay in registers as the
-// relu masks); rows that another thread needs go through LDS, and every row
-// the separate kernels stored is stored for cs_bwd_w and the tests.
-__global__ void __launch_bounds__(256)
-cs_head_kernel(CachedPtrs P, CachedDims D) {
-  constexpr int HS = HD_HS;
-  __shared__ float sW2p[KA * HD_ROW];
-  __shared__ float sW1p[KFC * KFIN], sW1v[KFC * KFIN], sWg[KGE * KGF];
-  __shared__ float sB2p[KA];
-  // backward rows; +1 keeps the HS rows of one column on distinct banks
-  __shared__ float sGL[HS][KA], sGV[HS], sGF[HS][KFIN];
-  __shared__ float sGHp[HS][KFC + 1], sGHv[HS][KFC + 1];
-  // forward rows
-  __shared__ float sFin[HS][KFIN], sHp[HS][HD_ROW], sVred[HS][KFC];
-  __shared__ float sGf[HS][KGF], sU34[HS][KGF];
-  __shared__ float sGamG[KGF], sBetG[KGF], sBg[KGE];
-  __shared__ float sPart[HS][KA][16 + 1];
-  __shared__ float sRow[HS][KA], sPp[HS][KA], sLp[HS][KA];
-  __shared__ float sVal[HS], sCoef[HS], sHent[HS];
-  const int tid = threadIdx.x;
-  constexpr int NT = 256;
-  for (int x = tid; x < KA * KFC; x += NT)
-    sW2p[(x / KFC) * HD_ROW + hd_pad(x % KFC)] = WP(W_P2_W)[x];
-  for (int x = tid; x < KGE * KGF; x += NT) sWg[x] = WP(W_G_W)[x];
-  if (tid < KA) sB2p[tid] = WP(W_P2_B)[tid];
-  if (tid < KGF) {
-    sGamG[tid] = WP(W_LN_G_W)[tid];
-    sBetG[tid] = WP(W_LN_G_B)[tid];
-  }
-  if (tid < KGE) sBg[tid] = WP(W_G_B)[tid];
-  float w1p[KFIN], w1v[KFIN];
-#pragma unroll
-  for (int i = 0; i < KFIN; ++i) {
-    w1p[i] = WP(W_P1_W)[tid * KFIN + i];
-    w1v[i] = WP(W_V1_W)[tid * KFIN + i];
-  }
-  // the backward's LDS copy of W1p / W1v comes out of the same registers:
-  // the block's threads hold exactly the two matrices, one row each
-#pragma unroll
-  for (int i = 0; i < KFIN; ++i) {
-    sW1p[tid * KFIN + i] = w1p[i];
-    sW1v[tid * KFIN + i] = w1v[i];
-  }
-  const float b1p = WP(W_P1_B)[tid], b1v = WP(W_V1_B)[tid];
-  const float w2v = WP(W_V2_W)[tid];
-  const float b2v = WP(W_V2_B)[0];
-  const float klc = P.kl[0];
-  const int wv = tid >> 6, ln = tid & 63;
-  const int per = (D.B + gridDim.x - 1) / gridDim.x;
-  const int b0 = blockIdx.x * per;
-  const int b1 = min(D.B, b0 + per);
-  for (int c0 = b0; c0 < b1; c0 += HS) {
-    const int ns = min(HS, b1 - c0);
-    // final = concat(pooled[model], graph_module(LN(gf))): the per-sample
-    // half of cs_fwd_pool_kernel.  The lanes of a sample walk its gf row
-    // redundantly for the LN sums (same bits in every lane).
-    for (int x = tid; x < ns * KGF; x += NT)
-      sGf[x / KGF][x % KGF] = P.gf[(long)c0 * KGF + x];
-    for (int x = tid; x < ns * KOUT; x += NT) {
-      const int s = x / KOUT, i = x % KOUT;
-      const long mid = P.model_ids[c0 + s];
-      const float pv = P.pooled[mid * KOUT + i];
-      sFin[s][i] = pv;
-      P.fin[(long)(c0 + s) * KFIN + i] = pv;
-    }
-    __syncthreads();
-    for (int x = tid; x < ns * KGF; x += NT) {
-      const int s = x / KGF, i = x % KGF;
-      const float* __restrict__ xr = sGf[s];
-      float sum = 0.f;
-#pragma unroll
-      for (int k = 0; k < KGF; ++k) sum = sum + xr[k];
-      const float mu = sum / KGF;
-      float var;
-      {
-        const float d0 = xr[0] - mu;
-        var = d0 * d0;
-      }
-#pragma unroll
-      for (int k = 1; k < KGF; ++k) {
-        const float d = xr[k] - mu;
-        var = var + d * d;
-      }
-      const float rstd = rsqrtf(var / KGF + LN_EPS);
-      const float xh = (xr[i] - mu) * rstd;
-      P.xh34[(long)(c0 + s) * KGF + i] = xh;
-      sU34[s][i] = FMA(xh, sGamG[i], sBetG[i]);
-    }
-    __syncthreads();
-    for (int x = tid; x < ns * KGE; x += NT) {
-      const int s = x / KGE, o = x % KGE;
-      float acc = sBg[o];
-#pragma unroll
-      for (int i = 0; i < KGF; ++i)
-        acc = FMA(sWg[o * KGF + i], sU34[s][i], acc);
-      sFin[s][KOUT + o] = acc;               // graph_module has NO activation
-      P.fin[(long)(c0 + s) * KFIN + KOUT + o] = acc;
-    }
-    __syncthreads();
-    // FC hidden layers: bias first, i ascending
-    float hp[HS], hv[HS];
-#pragma unroll
-    for (int s = 0; s < HS; ++s) {
-      hp[s] = 0.f;
-      hv[s] = 0.f;
-      if (s < ns) {
-        float ap = b1p, av = b1v;
-#pragma unroll
-        for (int i = 0; i < KFIN; ++i) {
-          ap = FMA(w1p[i], sFin[s][i], ap);
-          av = FMA(w1v[i], sFin[s][i], av);
-        }
-        ap = ap > 0.f ? ap : 0.f;
-        av = av > 0.f ? av : 0.f;
-        const long u = (long)(c0 + s) * KFC + tid;
-        P.h1p[u] = ap;
-        P.h1v[u] = av;
-        hp[s] = ap;
-        hv[s] = av;
-        sHp[s][hd_pad(tid)] = ap;
-        sVred[s][tid] = w2v * av;
-      }
-    }
-    __syncthreads();
-    // logit partials over the 16 chunks of the hidden row
-    for (int x = tid; x < ns * KA * 16; x += NT) {
-      const int s = x / (KA * 16), r = x % (KA * 16);
-      const int a = r / 16, c = r % 16;
-      const float* __restrict__ w = sW2p + a * HD_ROW + c * HD_CS;
-      const float* __restrict__ h = sHp[s] + c * HD_CS;
-      float acc = FMA(w[0], h[0], 0.f);
-#pragma unroll
-      for (int i = 1; i < 16; ++i) {
-        if (i < 4) acc = FMA(w[i], h[i], acc);
-        else acc = acc + w[i] * h[i];
-      }
-      sPart[s][a][c] = acc;
-    }
-    // value: wave s folds sample s's 256 products in the halving tree's
-    // pairing (t with t + 128, 64, ... 1)
-    if (wv < ns) {
-      const float* __restrict__ vr = sVred[wv];
-      float a0 = vr[ln] + vr[ln + 128];
-      const float a1 = vr[ln + 64] + vr[ln + 192];
-      a0 = a0 + a1;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1)
-        a0 = a0 + __shfl_down(a0, off, 64);
-      if (ln == 0) {
-        const float val = a0 + b2v;
-        sVal[wv] = val;
-        P.values[c0 + wv] = val;
-      }
-    }
-    __syncthreads();
-    // raw masked logits
-    for (int x = tid; x < ns * KA; x += NT) {
-      const int s = x / KA, a = x % KA;
-      float acc = sB2p[a];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) acc = acc + sPart[s][a][c];
-      const float fmin = -3.402823466e+38f;
-      float lm = logf(P.mask[(long)c0 * KA + x]);
-      if (!(lm > fmin)) lm = fmin;
-      sRow[s][a] = acc + lm;
-    }
-    __syncthreads();
-    // softmax / surrogate row of sample s: lane 0 of wave s
-    if (wv < ns && ln == 0) {
-      const int s = wv;
-      const int b = c0 + s;
-      const float* __restrict__ row = sRow[s];
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int a = 0; a < KA; ++a) mx = fmaxf(mx, row[a]);
-      float Z = 0.f;
-#pragma unroll
-      for (int a = 0; a < KA; ++a) Z = Z + __expf(row[a] - mx);
-      const float lse = mx + __logf(Z);
-      float ent = 0.f;
-#pragma unroll
-      for (int a = 0; a < KA; ++a) {
-        const float lp = row[a] - lse;
-        const float e = __expf(lp);
-        sLp[s][a] = lp;
-        sPp[s][a] = e;
-        ent = FMA(-lp, e, ent);
-      }
-      const long act = P.actions[b];
-      const float logp_a = sLp[s][act];
-      const float old_lp = P.old_logp[b];
-      const float ratio = __expf(logp_a - old_lp);
-      const float A_b = P.adv[b];
-      const float r_cl = fminf(fmaxf(ratio, 1.f - D.clip), 1.f + D.clip);
-      const float surr1 = ratio * A_b, surr2 = r_cl * A_b;
-      float ds = ratio * A_b;
-      if (surr2 < surr1 && (ratio < 1.f - D.clip || ratio > 1.f + D.clip))
-        ds = 0.f;
-      const float coef = -ds - klc;
-      P.hent[b] = ent;
-      P.coef[b] = coef;
-      sHent[s] = ent;
-      sCoef[s] = coef;
-    }
-    __syncthreads();
-    // loss backward rows (upstream grad = 1); p and lp go out here
-    for (int x = tid; x < ns * KA; x += NT) {
-      const int s = x / KA, a = x % KA;
-      const int b = c0 + s;
-      const long u = (long)b * KA + a;
-      const long act = P.actions[b];
-      const float c = sCoef[s] / D.B;
-      const float pj = sPp[s][a];
-      const float lpj = sLp[s][a];
-      P.p[u] = pj;
-      P.lp[u] = lpj;
-      const float delta = (a == (int)act) ? 1.f : 0.f;
-      const float gl = mul_rn(c, delta - pj)
-                       + mul_rn(mul_rn(D.ent_coef / D.B, pj),
-                                lpj + sHent[s]);
-      P.glogits[u] = gl;
-      sGL[s][a] = gl;
-    }
-    if (tid >= 128 && tid < 128 + ns) {
-      const int s = tid - 128;
-      const int b = c0 + s;
-      const float verr = sVal[s] - P.vtarg[b];
-      const float mk = (verr * verr <= D.vf_clip) ? 1.f : 0.f;
-      const float gv = D.vf_coef * 2.f * verr * mk / D.B;
-      P.gvalue[b] = gv;
-      sGV[s] = gv;
-    }
-    __syncthreads();
-    // hidden grads
-#pragma unroll
-    for (int s = 0; s < HS; ++s) {
-      if (s < ns) {
-        const int j = tid;
-        const long u = (long)(c0 + s) * KFC + j;
-        float acc = 0.f;
-#pragma unroll
-        for (int a = 0; a < KA; ++a) {
-          // the first five terms are fused, the rest rounded products
-          const float w = sW2p[a * HD_ROW + hd_pad(j)];
-          if (a < 5) acc = FMA(w, sGL[s][a], acc);
-          else acc = acc + mul_rn(w, sGL[s][a]);
-        }
-        const float gp = hp[s] > 0.f ? acc : 0.f;
-        const float av = w2v * sGV[s];
-        const float gv = hv[s] > 0.f ? av : 0.f;
-        P.gh1p[u] = gp;
-        P.gh1v[u] = gv;
-        sGHp[s][j] = gp;
-        sGHv[s][j] = gv;
-      }
-    }
-    __syncthreads();
-    // gfinal: one thread per (sample, i), j = 0..FC-1 in order
-    for (int x = tid; x < ns * KFIN; x += NT) {
-      const int s = x / KFIN, i = x % KFIN;
-      float acc = 0.f;
-#pragma unroll 8
-      for (int j = 0; j < KFC; ++j) {
-        acc = FMA(sW1p[j * KFIN + i], sGHp[s][j], acc);
-        acc = FMA(sW1v[j * KFIN + i], sGHv[s][j], acc);
-      }
-      P.gfinal[(long)(c0 + s) * KFIN + i] = acc;
-      sGF[s][i] = acc;
-    }
-    __syncthreads();
-    // graph-module LN-out grads
-    for (int x = tid; x < ns * KGF; x += NT) {
-      const int s = x / KGF, i = x % KGF;
-      float acc = 0.f;
-#pragma unroll
-      for (int o = 0; o < KGE; ++o)
-        acc = acc + mul_rn(sWg[o * KGF + i], sGF[s][KOUT + o]);
-      P.gu34[(long)(c0 + s) * KGF + i] = acc;
-    }
-    // no barrier here: every row buffer's next write is at least one
-    // barrier after its last read above
-  }
-  // the logging-only C_STATS sums are taken from the stored rows by the
-  // statistics blocks of cs_bwd_scat1_gu1_kernel
-}
-
-// ---- cs_head with a shorter chain (DDLS_AMD_STEP_HEAD, default on) ----
-// cs_head_kernel's phases, arithmetic and stores, term for term; the kernel
-// above stays unchanged as the oracle.  What changes is what sits on the
-// block's serial chain:
+// min(B, HD2_MAXB) blocks, each walking its contiguous sample range HS = 1
+// sample at a time (the chunk loop and the [HS] row buffers allow more).
+// Thread j owns hidden unit j of both branches through the forward AND the
+// backward (h1p/h1v stay in registers as the relu masks); rows that another
+// thread needs go through LDS, and every row the reference kernels store is
+// stored for the weight grads and the tests.  What sits on the block's serial
+// chain is kept short:
 //  * every per-sample input of a chunk (mask, actions, old_logp, adv, vtarg)
 //    is loaded at the chunk's top, in the round trip of gf / model_ids, not
 //    in the middle of the chain (logf(mask) is taken there too);
 //  * the gfinal phase reads its W1p / W1v copies i-major ([i][j], row stride
 //    HD2_WS) and the hidden-grad rows with 16-byte LDS reads: 4 reads per
-//    four j instead of 16.  The chain order stays j = 0..255, policy term
-//    then value term, all fused.  Thread j writes column j of the copies, so
-//    the writes are conflict-free;
-//  * one sample a block on min(B, HD2_MAXB) blocks instead of four on
-//    min(B, 32): the FC-hidden, logit-partial and hidden-grad phases are as
-//    many times as long per thread as a block has samples in flight, and the
-//    other CUs idle anyway.  The chunk loop and the [HS] row buffers are the
-//    oracle's, with HS = 1; traces of 4, 2 and 1 samples a block at B = 128
-//    are in docs/KERNELS.md, "Round 9".
+//    four j.  The chain order is j = 0..255, policy term then value term,
+//    all fused.  Thread j writes column j of the copies, so the writes are
+//    conflict-free;
+//  * one sample a block: the FC-hidden, logit-partial and hidden-grad phases
+//    are as many times as long per thread as a block has samples in flight,
+//    and the other CUs idle anyway; traces of 4, 2 and 1 samples a block at
+//    B = 128 are in docs/KERNELS.md, "Round 9".
+// "cs_head_kernel" and "the oracle" in comments inside the bodies of this
+// kernel and of cs_bwd_pool_wfc2_kernel mean their predecessors, four samples
+// a block and 16 FC columns a block (removed; docs/KERNELS.md, "Paths and
+// switch"); the bodies are kept textually unchanged.
 #define HD2_WS (KFC + 4)           // 16-byte aligned, rows 4 banks apart
 #define HD2_MAXB 128
 #define LDS4(p) (*reinterpret_cast<const float4*>(p))   // 16-byte LDS read
@@ -2429,7 +2060,7 @@ cs_head2_kernel(CachedPtrs P, CachedDims D) {
 // ---- cs_fwd_combine<2> + the per-model means of cs_fwd_pool ----
 // One block per model: its nodes' h2 rows are computed into the LDS tile
 // (and written out), then unit i adds them in node order, as a chain out of
-// LDS.  The per-sample half of cs_fwd_pool_kernel is in cs_head_kernel.
+// LDS.  The per-sample half of cs_fwd_pool_kernel is in cs_head2_kernel.
 __global__ void __launch_bounds__(256)
 cs_fwd_comb2_pool_kernel(CachedPtrs P, CachedDims D) {
   constexpr int PT = 256;   // node rows of h2 per tile
@@ -2462,7 +2093,7 @@ cs_fwd_comb2_pool_kernel(CachedPtrs P, CachedDims D) {
   if (tid < KOUT) P.pooled[(long)m * KOUT + tid] = acc / (float)(hi - lo);
 }
 
-// ---- cs_fwd_combine<1> inside cs_fwd_mlp_lanes<2>'s staging loop ----
+// ---- cs_fwd_combine<1> inside the round-2 modules' staging loop ----
 // The node rows of the block are h1 rows: each staged element is computed
 // here, (rs1[v] + sum over the in-edges in CSR order of re1) / (deg + 1),
 // 0 without in-edges, and written to h1 for the backward.
@@ -2497,7 +2128,7 @@ cs_fwd_comb1_mlp2_lanes_kernel(CachedPtrs P, CachedDims D) {
   }
 }
 
-// ---- cs_bwd_scatter<2> inside cs_bwd_mlp2_lanes's staging loop ----
+// ---- cs_bwd_scatter<2> inside the round-2 modules' backward staging loop ----
 // ghn2[v] = gms2[v][:KH] + sum over the out-edges in src-CSR order of
 // gme2[.][:KH]; ghe2[k] = gme2[k][KH:].  Both are still written out.
 template <int L>
@@ -2538,7 +2169,7 @@ cs_bwd_scat2_mlp2_lanes_kernel(CachedPtrs P, CachedDims D) {
 // chain (all fused, from 0, o ascending).
 //
 // The grid's last block takes the C_STATS sums (logging only), which
-// cs_head_kernel leaves out.  It recomputes cs_fwd_loss_kernel's four terms
+// cs_head2_kernel leaves out.  It recomputes cs_fwd_loss_kernel's four terms
 // per sample from the stored rows (lp, values, hent: the same single
 // operations, so the same bits), sums them per group of 32 samples in sample
 // order, as that kernel's blocks do in LDS, and one thread adds the group
@@ -2651,432 +2282,53 @@ cs_bwd_scat1_gu1_kernel(CachedPtrs P, CachedDims D) {
 }
 
 // ===========================================================================
-// work off the serial chain (DDLS_AMD_STEP_OVERLAP, default on)
+// work off the serial chain
 // ===========================================================================
 //
-// A replay is one serial chain of launches.  Two pieces of work sat on it
-// although nothing ahead of them in the chain produces their inputs; each now
+// A replay is one serial chain of launches.  Two pieces of work would sit on
+// it although nothing ahead of them in the chain produces their inputs; each
 // rides as extra blocks of a launch that exists anyway (different roles per
 // block index, like the statistics block of cs_bwd_scat1_gu1_kernel), so the
 // chain stays serial and every output element keeps its summation order.
 
 // ---- cs_bwd_pool + the B-row ("special") blocks of cs_bwd_w ----
 // Blocks [0, M): pool role, one block per model.  Block M: the graph-module
-// weight-grad job.  Blocks M+1 .. M+16: the FC-column jobs.  The special jobs
-// read only what cs_head_kernel wrote, so they run here, five launches
-// earlier than in cs_bwd_w_kernel, which is then launched with its row-job
-// blocks only.  Arithmetic is that of cs_bwd_pool_kernel and of
-// cs_bwd_w_kernel's special blocks, term for term; what changes is the
-// staging: a super-tile of up to WFC_ST sample rows per global round trip
-// instead of TILE_K, walked in TILE_K-row tiles so a chain sees the same
-// full / partial tiles as before.
+// weight-grad job.  Blocks M+1 .. M+WFC2_NFC: the FC-column jobs.  The
+// special jobs read only what cs_head2_kernel wrote, so they run here, five
+// launches earlier than in the reference path's cs_bwd_w_kernel, which the
+// production path launches with its row-job blocks only.  Arithmetic is that
+// of cs_bwd_pool_kernel and of cs_bwd_w_kernel's special blocks, term for
+// term; the staging differs: a super-tile of up to WFC_ST sample rows per
+// global round trip instead of TILE_K, walked in TILE_K-row tiles so a chain
+// sees the same full / partial tiles.
 #define WFC_ST 128        // sample rows per super-tile (a multiple of TILE_K)
-#define WFC_NFC 16        // FC-column blocks
-// LDS floats per role; the kernel's buffer is their maximum (a union)
-#define WFC_LDS_POOL (1024 + WFC_ST * KOUT + KOUT)
-#define WFC_LDS_G (WFC_ST * (KGE + 3 * KGF))
-#define WFC_LDS_FC (WFC_ST * (KFIN + 4 * 16 + KA + 1))
-#define WFC_LDS (WFC_LDS_G > WFC_LDS_FC ? WFC_LDS_G : WFC_LDS_FC)
-static_assert(WFC_LDS >= WFC_LDS_POOL, "pool role LDS");
-static_assert(WFC_LDS * 4 <= 64 * 1024, "cs_bwd_pool_wfc: LDS over 64 KB");
 static_assert(WFC_ST % TILE_K == 0, "super-tile of whole tiles");
-static_assert(KFC / WFC_NFC == 16 && KFC % WFC_NFC == 0, "16 columns a block");
 
-__global__ void __launch_bounds__(256)
-cs_bwd_pool_wfc_kernel(CachedPtrs P, CachedDims D) {
-  __shared__ float lds[WFC_LDS];
-  const int tid = threadIdx.x;
-  constexpr int NT = 256;
-  const int bid = blockIdx.x;
-
-  if (bid < D.M) {
-    // ---- pool role: gpool[m] and this model's gh2 rows ----
-    const int m = bid;
-    int* smid = reinterpret_cast<int*>(lds);            // [1024]
-    float (*sG)[KOUT] = reinterpret_cast<float (*)[KOUT]>(lds + 1024);
-    float* sP = lds + 1024 + WFC_ST * KOUT;             // [KOUT]
-    // read ahead of the chain; used after it
-    const long lo = P.model_nptr[m], hi = P.model_nptr[m + 1];
-    for (int b = tid; b < D.B; b += NT) smid[b] = (int)P.model_ids[b];
-    float acc = 0.f;
-    for (int t0 = 0; t0 < D.B; t0 += WFC_ST) {
-      const int bt = min(WFC_ST, D.B - t0);
-      float rG[WFC_ST * KOUT / NT];
-#pragma unroll
-      for (int k = 0; k < WFC_ST * KOUT / NT; ++k) {
-        const int x = min(tid + k * NT, bt * KOUT - 1);
-        rG[k] = P.gfinal[(long)(t0 + x / KOUT) * KFIN + x % KOUT];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < WFC_ST * KOUT / NT; ++k) {
-        const int x = tid + k * NT;
-        if (x < bt * KOUT) sG[x / KOUT][x % KOUT] = rG[k];
-      }
-      __syncthreads();
-      if (tid < KOUT) {
-        if (bt == WFC_ST) {
-#pragma unroll 8
-          for (int b = 0; b < WFC_ST; ++b)
-            acc += (smid[t0 + b] == m) ? sG[b][tid] : 0.f;
-        } else {
-          for (int b = 0; b < bt; ++b)
-            acc += (smid[t0 + b] == m) ? sG[b][tid] : 0.f;
-        }
-      }
-    }
-    if (tid < KOUT) {
-      P.gpool[(long)m * KOUT + tid] = acc;
-      sP[tid] = acc;
-    }
-    __syncthreads();
-    const float nn = (float)(hi - lo);
-    for (long u = lo * KOUT + tid; u < hi * KOUT; u += NT)
-      P.gh2[u] = sP[u % KOUT] / nn;
-    return;
-  }
-
-  if (bid == D.M) {
-    // ---- graph module: Wg[GEMB,GFin], bg; LN gamma/beta from gu34 + xh34.
-    // gpre rows are gfinal[:, KOUT:KOUT+KGE] (row stride KFIN).
-    float (*tG)[KGE] = reinterpret_cast<float (*)[KGE]>(lds);
-    float (*tU)[KGF] = reinterpret_cast<float (*)[KGF]>(lds + WFC_ST * KGE);
-    float (*tXH)[KGF] =
-        reinterpret_cast<float (*)[KGF]>(lds + WFC_ST * (KGE + KGF));
-    float (*tGU)[KGF] =
-        reinterpret_cast<float (*)[KGF]>(lds + WFC_ST * (KGE + 2 * KGF));
-    const float* __restrict__ gam = WP(W_LN_G_W);
-    const float* __restrict__ bet = WP(W_LN_G_B);
-    constexpr int UNITS = KGE * KGF;
-    constexpr int MYU = (UNITS + 255) / 256;
-    float acc[MYU];
-#pragma unroll
-    for (int q = 0; q < MYU; ++q) acc[q] = 0.f;
-    // tid in [64, 64+KGE): bias sums; tid in [128, 128+KGF): LN gamma/beta
-    float bacc = 0.f, lacc_w = 0.f, lacc_b = 0.f;
-    for (int r0 = 0; r0 < D.B; r0 += WFC_ST) {
-      const int rt = min(WFC_ST, D.B - r0);
-      // Every global load of the super-tile is issued before the first LDS
-      // store: constant trip counts, indices clamped instead of branched on
-      // so the loads share a basic block.  One round trip per super-tile.
-      {
-        constexpr int CG = WFC_ST * KGE / NT, CX = WFC_ST * KGF / NT;
-        static_assert(CG * NT == WFC_ST * KGE && CX * NT == WFC_ST * KGF,
-                      "whole trips");
-        float rG[CG], rXH[CX], rGU[CX], rGam[CX], rBet[CX];
-#pragma unroll
-        for (int k = 0; k < CG; ++k) {
-          const int x = min(tid + k * NT, rt * KGE - 1);
-          rG[k] = P.gfinal[(long)(r0 + x / KGE) * KFIN + KOUT + x % KGE];
-        }
-#pragma unroll
-        for (int k = 0; k < CX; ++k) {
-          const int x = min(tid + k * NT, rt * KGF - 1);
-          rXH[k] = P.xh34[(long)r0 * KGF + x];
-          rGU[k] = P.gu34[(long)r0 * KGF + x];
-          rGam[k] = gam[x % KGF];
-          rBet[k] = bet[x % KGF];
-        }
-#pragma unroll
-        for (int k = 0; k < CG; ++k) {
-          const int x = tid + k * NT;
-          if (x < rt * KGE) tG[x / KGE][x % KGE] = rG[k];
-        }
-#pragma unroll
-        for (int k = 0; k < CX; ++k) {
-          const int x = tid + k * NT;
-          if (x < rt * KGF) {
-            const int t = x / KGF, i = x % KGF;
-            tU[t][i] = FMA(rXH[k], rGam[k], rBet[k]);
-            tXH[t][i] = rXH[k];
-            tGU[t][i] = rGU[k];
-          }
-        }
-      }
-      __syncthreads();
-      // a full super-tile has constant trip counts: the LDS reads of a chain
-      // run ahead of its adds
-#pragma unroll
-      for (int q = 0; q < MYU; ++q) {
-        int u = tid + q * 256;
-        if (u < UNITS) {
-          int o = u / KGF, i = u % KGF;
-          float a = acc[q];
-          if (rt == WFC_ST) {
-#pragma unroll 16
-            for (int t = 0; t < WFC_ST; ++t) a = FMA(tG[t][o], tU[t][i], a);
-          } else {
-            for (int t = 0; t < rt; ++t) a = FMA(tG[t][o], tU[t][i], a);
-          }
-          acc[q] = a;
-        }
-      }
-      if (tid >= 64 && tid < 64 + KGE) {
-        if (rt == WFC_ST) {
-#pragma unroll 16
-          for (int t = 0; t < WFC_ST; ++t) bacc = bacc + tG[t][tid - 64];
-        } else {
-          for (int t = 0; t < rt; ++t) bacc = bacc + tG[t][tid - 64];
-        }
-      }
-      if (tid >= 128 && tid < 128 + KGF) {
-        if (rt == WFC_ST) {
-#pragma unroll 16
-          for (int t = 0; t < WFC_ST; ++t) {
-            lacc_w = lacc_w + mul_rn(tGU[t][tid - 128], tXH[t][tid - 128]);
-            lacc_b = lacc_b + tGU[t][tid - 128];
-          }
-        } else {
-          for (int t = 0; t < rt; ++t) {
-            lacc_w = lacc_w + mul_rn(tGU[t][tid - 128], tXH[t][tid - 128]);
-            lacc_b = lacc_b + tGU[t][tid - 128];
-          }
-        }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < MYU; ++q) {
-      int u = tid + q * 256;
-      if (u < UNITS) WG_(W_G_W)[u] = acc[q];
-    }
-    if (tid >= 64 && tid < 64 + KGE) WG_(W_G_B)[tid - 64] = bacc;
-    if (tid >= 128 && tid < 128 + KGF) {
-      WG_(W_LN_G_W)[tid - 128] = lacc_w;
-      WG_(W_LN_G_B)[tid - 128] = lacc_b;
-    }
-    return;
-  }
-
-  // ---- FC-column jobs: block jb owns columns [j0, j0 + 16) of W1p/W1v
-  // [FC,FIN] (+ b1p/b1v) AND of W2p [A,FC] / W2v [FC]; block 0 also sums b2p
-  // and b2v.
-  {
-    constexpr int JW = KFC / WFC_NFC;   // 16
-    const int jb = bid - D.M - 1;
-    if (jb >= WFC_NFC) return;
-    const int j0 = jb * JW;
-    float* q_ = lds;
-    float (*tF)[KFIN] = reinterpret_cast<float (*)[KFIN]>(q_);
-    q_ += WFC_ST * KFIN;
-    float (*tGp)[16] = reinterpret_cast<float (*)[16]>(q_);
-    q_ += WFC_ST * 16;
-    float (*tGv)[16] = reinterpret_cast<float (*)[16]>(q_);
-    q_ += WFC_ST * 16;
-    float (*tHp)[16] = reinterpret_cast<float (*)[16]>(q_);
-    q_ += WFC_ST * 16;
-    float (*tHv)[16] = reinterpret_cast<float (*)[16]>(q_);
-    q_ += WFC_ST * 16;
-    float (*tGL)[KA] = reinterpret_cast<float (*)[KA]>(q_);
-    q_ += WFC_ST * KA;
-    float* tGV = q_;                                    // [WFC_ST]
-    constexpr int MYU = (16 * KFIN + 255) / 256;
-    constexpr int MYU2 = (16 * KA + 255) / 256;
-    float accp[MYU], accv[MYU], acc2[MYU2];
-#pragma unroll
-    for (int q = 0; q < MYU; ++q) { accp[q] = 0.f; accv[q] = 0.f; }
-#pragma unroll
-    for (int q = 0; q < MYU2; ++q) acc2[q] = 0.f;
-    // The single-chain sums sit in the waves with the fewest weight units
-    // (units fill tid 0.. upwards).  tid in [192, 192+JW): column sums
-    // b1p/b1v and the W2v column; jb == 0 only: tid in [128, 128+KA) sums
-    // b2p, tid == 128+KA sums b2v
-    const int cj = tid - 192;
-    float bp = 0.f, bv = 0.f, w2v = 0.f, b2 = 0.f;
-    for (int s0 = 0; s0 < D.B; s0 += WFC_ST) {
-      const int st = min(WFC_ST, D.B - s0);
-      // as in the graph-module role: all global loads of the super-tile
-      // first (clamped indices, one basic block), then the LDS stores
-      {
-        constexpr int CF = WFC_ST * KFIN / NT, CJ = WFC_ST * JW / NT;
-        constexpr int CL = (WFC_ST * KA + NT - 1) / NT;
-        static_assert(CF * NT == WFC_ST * KFIN && CJ * NT == WFC_ST * JW
-                      && WFC_ST <= NT, "whole trips");
-        float rF[CF], rGp[CJ], rGv[CJ], rHp[CJ], rHv[CJ], rGL[CL];
-#pragma unroll
-        for (int k = 0; k < CF; ++k) {
-          const int x = min(tid + k * NT, st * KFIN - 1);
-          rF[k] = P.fin[(long)s0 * KFIN + x];
-        }
-#pragma unroll
-        for (int k = 0; k < CJ; ++k) {
-          const int x = min(tid + k * NT, st * JW - 1);
-          const long g = (long)(s0 + x / JW) * KFC + j0 + x % JW;
-          rGp[k] = P.gh1p[g];
-          rGv[k] = P.gh1v[g];
-          rHp[k] = P.h1p[g];
-          rHv[k] = P.h1v[g];
-        }
-#pragma unroll
-        for (int k = 0; k < CL; ++k) {
-          const int x = min(tid + k * NT, st * KA - 1);
-          rGL[k] = P.glogits[(long)s0 * KA + x];
-        }
-        const float rGV = P.gvalue[s0 + min(tid, st - 1)];
-#pragma unroll
-        for (int k = 0; k < CF; ++k) {
-          const int x = tid + k * NT;
-          if (x < st * KFIN) tF[x / KFIN][x % KFIN] = rF[k];
-        }
-#pragma unroll
-        for (int k = 0; k < CJ; ++k) {
-          const int x = tid + k * NT;
-          if (x < st * JW) {
-            const int t = x / JW, j = x % JW;
-            tGp[t][j] = rGp[k];
-            tGv[t][j] = rGv[k];
-            tHp[t][j] = rHp[k];
-            tHv[t][j] = rHv[k];
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < CL; ++k) {
-          const int x = tid + k * NT;
-          if (x < st * KA) tGL[x / KA][x % KA] = rGL[k];
-        }
-        if (tid < st) tGV[tid] = rGV;
-      }
-      __syncthreads();
-      // the super-tile in TILE_K-row tiles: each chain sees the full and
-      // partial tiles cs_bwd_w_kernel's special blocks saw
-      for (int r0 = 0; r0 < st; r0 += TILE_K) {
-        const int rt = min(TILE_K, st - r0);
-#pragma unroll
-        for (int q = 0; q < MYU; ++q) {
-          int u = tid + q * NT;
-          if (u < JW * KFIN) {
-            int j = u / KFIN, i = u % KFIN;
-            float ap = accp[q], av = accv[q];
-            if (rt == TILE_K) {
-#pragma unroll
-              for (int t = 0; t < TILE_K; ++t) {
-                ap = FMA(tGp[r0 + t][j], tF[r0 + t][i], ap);
-                av = FMA(tGv[r0 + t][j], tF[r0 + t][i], av);
-              }
-            } else {
-              for (int t = 0; t < rt; ++t) {
-                ap = FMA(tGp[r0 + t][j], tF[r0 + t][i], ap);
-                av = FMA(tGv[r0 + t][j], tF[r0 + t][i], av);
-              }
-            }
-            accp[q] = ap;
-            accv[q] = av;
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < MYU2; ++q) {
-          int u = tid + q * NT;
-          if (u < KA * JW) {
-            int a = u / JW, j = u % JW;
-            float s = acc2[q];
-            if (rt == TILE_K) {
-#pragma unroll
-              for (int t = 0; t < TILE_K; ++t) {
-                // a full tile's first 20 terms are fused, the last 12 are
-                // rounded products; a partial tile is fused throughout
-                if (t < 20) s = FMA(tGL[r0 + t][a], tHp[r0 + t][j], s);
-                else s = s + mul_rn(tGL[r0 + t][a], tHp[r0 + t][j]);
-              }
-            } else {
-              for (int t = 0; t < rt; ++t)
-                s = FMA(tGL[r0 + t][a], tHp[r0 + t][j], s);
-            }
-            acc2[q] = s;
-          }
-        }
-      }
-      if (cj >= 0 && cj < JW) {
-        if (st == WFC_ST) {
-#pragma unroll 16
-          for (int t = 0; t < WFC_ST; ++t) {
-            bp = bp + tGp[t][cj];
-            bv = bv + tGv[t][cj];
-            w2v = FMA(tGV[t], tHv[t][cj], w2v);
-          }
-        } else {
-          for (int t = 0; t < st; ++t) {
-            bp = bp + tGp[t][cj];
-            bv = bv + tGv[t][cj];
-            w2v = FMA(tGV[t], tHv[t][cj], w2v);
-          }
-        }
-      }
-      if (jb == 0) {
-        if (tid >= 128 && tid < 128 + KA) {
-          if (st == WFC_ST) {
-#pragma unroll 16
-            for (int t = 0; t < WFC_ST; ++t) b2 = b2 + tGL[t][tid - 128];
-          } else {
-            for (int t = 0; t < st; ++t) b2 = b2 + tGL[t][tid - 128];
-          }
-        }
-        if (tid == 128 + KA) {
-          if (st == WFC_ST) {
-#pragma unroll 16
-            for (int t = 0; t < WFC_ST; ++t) b2 = b2 + tGV[t];
-          } else {
-            for (int t = 0; t < st; ++t) b2 = b2 + tGV[t];
-          }
-        }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < MYU; ++q) {
-      int u = tid + q * NT;
-      if (u < JW * KFIN) {
-        int j = u / KFIN, i = u % KFIN;
-        WG_(W_P1_W)[(long)(j0 + j) * KFIN + i] = accp[q];
-        WG_(W_V1_W)[(long)(j0 + j) * KFIN + i] = accv[q];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < MYU2; ++q) {
-      int u = tid + q * NT;
-      if (u < KA * JW) {
-        int a = u / JW, j = u % JW;
-        WG_(W_P2_W)[(long)a * KFC + j0 + j] = acc2[q];
-      }
-    }
-    if (cj >= 0 && cj < JW) {
-      WG_(W_P1_B)[j0 + cj] = bp;
-      WG_(W_V1_B)[j0 + cj] = bv;
-      WG_(W_V2_W)[j0 + cj] = w2v;
-    }
-    if (jb == 0) {
-      if (tid >= 128 && tid < 128 + KA) WG_(W_P2_B)[tid - 128] = b2;
-      if (tid == 128 + KA) WG_(W_V2_B)[0] = b2;
-    }
-  }
-}
-
-// ---- cs_bwd_pool_wfc with shorter roles (DDLS_AMD_STEP_HEAD, default on) ----
-// Same launch, same outputs, same bits as cs_bwd_pool_wfc_kernel above, which
-// stays unchanged as the oracle (DDLS_AMD_STEP_HEAD=off launches it).  The
-// launch lasts as long as its slowest block, and every role's time is issue
-// slots of one wave: LDS reads and dependent FMAs.  What changes:
+// The launch lasts as long as its slowest block, and every role's time is
+// issue slots of one wave: LDS reads and dependent FMAs.  So:
 //
-//  * FC-column role: WFC2_JW columns a block instead of 16 (KFC / WFC2_JW
-//    blocks instead of 16), so no thread carries more than one weight unit,
-//    and the weight units, the W2p units and the single-chain sums sit in
-//    different waves where the block has room.  Columns are independent
-//    outputs: no partial sums, no reduce, every chain keeps its term order.
+//  * FC-column role: WFC2_JW columns a block (KFC / WFC2_JW blocks), so no
+//    thread carries more than one weight unit, and the weight units, the W2p
+//    units and the single-chain sums sit in different waves where the block
+//    has room.  Columns are independent outputs: no partial sums, no reduce,
+//    every chain keeps its term order.
 //  * Sample-major tiles are stored transposed ([column][sample], row stride
 //    WFC2_TS), so a chain reads four consecutive samples of an operand with
-//    one 16-byte LDS read: 3 reads + 8 FMAs per four terms of a W1p/W1v unit
-//    instead of 12 + 8.  The terms are still consumed in sample order.
+//    one 16-byte LDS read: 3 reads + 8 FMAs per four terms of a W1p/W1v unit.
+//    The terms are still consumed in sample order.
 //  * Graph-module role: the same transposed layout and 16-byte reads.
 //  * Pool role: wave 0 lists the model's samples once, in sample order, and
-//    the chain then adds only those.  The oracle adds +0 for every other
-//    sample.  Its accumulator starts at +0, and a round-to-nearest sum is -0
-//    only when both addends are -0, so the accumulator is never -0 and adding
-//    +0 to it never changes it: leaving those terms out gives the same bits.
+//    the chain then adds only those.  cs_bwd_pool_kernel adds +0 for every
+//    other sample.  Its accumulator starts at +0, and a round-to-nearest sum
+//    is -0 only when both addends are -0, so the accumulator is never -0 and
+//    adding +0 to it never changes it: leaving those terms out gives the same
+//    bits.
 //  * The weight slot offsets are loaded once at the top of a block, in the
 //    same round trip as the first tile, not in front of the final stores.
 //
-// Tile pattern of the W2p units as in the oracle: the super-tile is walked in
-// TILE_K-row tiles; a full tile's terms 0-19 are fused and 20-31 are rounded
-// products, a partial tile is fused throughout.
+// Tile pattern of the W2p units as in cs_bwd_w_kernel: the super-tile is
+// walked in TILE_K-row tiles; a full tile's terms 0-19 are fused and 20-31
+// are rounded products, a partial tile is fused throughout.
 #define WFC2_JW 4                       // FC columns per block
 #define WFC2_NFC (KFC / WFC2_JW)        // FC-column blocks
 #define WFC2_TS (WFC_ST + 4)            // transposed row stride (16 B aligned)
@@ -3515,51 +2767,20 @@ cs_bwd_pool_wfc2_kernel(CachedPtrs P, CachedDims D) {
   }
 }
 
-// ---- cs_stage + cs_fwd_mlp_lanes<1> ----
-// Block 0 gathers the minibatch from the device batch store (the body of
-// cs_stage_kernel, one workgroup, same cursor protocol and guards); blocks
-// 1.. are cs_fwd_mlp_lanes_kernel<1, L>'s blocks 0.. .  No GNN forward kernel
-// reads a staged buffer (cs_head_kernel is their first reader), so the two
-// roles are independent and one launch of the chain goes away.
 static_assert(CS_STAGE_THREADS == ROW_NT, "stage role runs a ROW_NT block");
-
-template <int L>
-__global__ void __launch_bounds__(ROW_NT)
-cs_fwd_stage_mlp1_lanes_kernel(CachedPtrs P, CachedDims D, StagePtrs SP,
-                               StageDims SD) {
-  if (blockIdx.x == 0) {
-    cs_stage_body(SP, SD);
-    return;
-  }
-  constexpr int RPB = ROW_NT / L;
-  const int blk = (int)blockIdx.x - 1;
-  const int nbN = (D.N + RPB - 1) / RPB;
-  if (blk < nbN) {
-    const long r0 = (long)blk * RPB;
-    rows_fwd_lanes<KF0, KH, 1, L>(
-        P, W_LN_N1_W, r0, D.N,
-        [&](long v, int i) { return P.z0[v * KF0 + i]; },
-        P.xh_z1, P.rst_z1, P.hn1);
-  } else {
-    const long r0 = (long)(blk - nbN) * RPB;
-    rows_fwd_lanes<KFE, KH, 0, L>(
-        P, W_LN_E1_W, r0, D.E,
-        [&](long k, int i) { return P.e[k * KFE + i]; },
-        P.xh_e1, P.rst_e1, P.he1);
-  }
-}
 
 // ---- cs_stage + round-1 node / edge modules + round-1 reduce module ----
 // The round-1 modules are 5 -> 16 and 2 -> 16: a reduce-module block can
 // compute hn1[src[k]] and he1[k] for its own message rows from z0 / e while
 // it stages them, which is cheaper than a launch of its own and a
 // src -> hn1 gather through memory.  Block 0 (with a device batch store) is
-// the stage role; then cs_fwd_reduce_lanes_kernel<1, L>'s edge-row and
-// self-row blocks.  Every tensor the two launches stored is still stored,
+// the stage role (the body of cs_stage_kernel, one workgroup, same cursor
+// protocol and guards; no GNN forward kernel reads a staged buffer, so the
+// roles are independent); then the reduce module's edge-row and self-row
+// blocks.  Every tensor cs_fwd_mlp<1> and cs_fwd_reduce<1> store is stored,
 // once: he1 / xh_e1 / rst_e1 by the edge block that owns the edge, hn1 /
 // xh_z1 / rst_z1 by the self-row block that owns the node (an edge block
-// recomputes hn1[src] and does not store it).  DDLS_AMD_STEP_MERGE=off
-// launches the two kernels above.
+// recomputes hn1[src] and does not store it).
 
 // one output element of a round-1 module row: rows_fwd_lanes<Din, KH, NF, .>'s
 // operation sequence on the Din inputs at x; *xh_c is xhat[c]
@@ -4098,51 +3319,44 @@ cs_bwd_scat1_gu1_w_kernel(CachedPtrs P, CachedDims D) {
 // host bindings
 // ===========================================================================
 
-// Row-kernel selection, read per call like DDLS_AMD_WGRAD_MFMA:
-//   DDLS_AMD_ROW_KERNELS=thread  the thread-per-row kernels (oracle / A/B)
+// Path selection, read per call like DDLS_AMD_WGRAD_MFMA:
+//   DDLS_AMD_STEP_PATH=production|reference
+//                                unset or empty: production.  'reference'
+//                                launches the thread-per-row and separate
+//                                kernels (the header comment lists both).
 //   DDLS_AMD_ROW_LANES=8|16|32   lanes per row for ALL lane-parallel kernels
-//                                (measurement switch).  Unset: each launch's
-//                                own default, the best of the three as
-//                                measured on MI355X at the benchmark's 417
-//                                rows (docs/KERNELS.md "Round 5"): 32 for the
-//                                two 32x64 reduce-module-1 kernels, else 16.
-//   DDLS_AMD_STEP_FUSION=off     the separate kernels of every fused launch
-//                                (oracle / A/B); 'thread' above implies it
-//   DDLS_AMD_STEP_OVERLAP=off    cs_stage, cs_bwd_pool and the B-row blocks
-//                                of cs_bwd_w as launches / blocks of their
-//                                own (oracle / A/B); STEP_FUSION=off and
-//                                'thread' imply it
-//   DDLS_AMD_STEP_MERGE=off      cs_fwd_stage_mlp1_lanes + cs_fwd_reduce_lanes<1>
-//                                and cs_bwd_scat1_gu1 + cs_bwd_w as two
-//                                launches each, and cs_bwd_w_reduce always
-//                                launched by cached_step_bwd (oracle / A/B);
-//                                STEP_OVERLAP=off, STEP_FUSION=off and
-//                                'thread' imply it
-//   DDLS_AMD_STEP_HEAD=off       cs_head and cs_bwd_pool_wfc in place of
-//                                cs_head2 and cs_bwd_pool_wfc2 (oracle /
-//                                A/B); STEP_MERGE=off and whatever implies it
-//                                imply this too.  The new kernels do not
-//                                depend on DDLS_AMD_WGRAD_MFMA and stay the
-//                                default with it.
+//                                of the production path (measurement switch).
+//                                Unset: each launch's own default, the best of
+//                                the three as measured on MI355X at the
+//                                benchmark's 417 rows (docs/KERNELS.md
+//                                "Round 5"): 32 for the two 32x64
+//                                reduce-module-1 kernels, else 16.
 struct RowCfg {
-  bool thread;
+  bool reference;
   int lanes;   // 0: per-kernel default
-  bool fused;  // the fused launches (needs the lane-parallel row kernels)
-  bool overlap;  // independent work rides in launches that exist anyway
-                 // (needs the fused launches)
-  bool merge;    // launches merged along row-local dependencies (needs
-                 // overlap)
-  bool head;     // cs_head2 / cs_bwd_pool_wfc2 (needs merge)
 };
+
+// NAME = prod | ref, unset or empty: prod.  True for ref.
+static bool path_switch(const char* name, const char* prod, const char* ref) {
+  const char* v = getenv(name);
+  const bool is_ref = (v != nullptr && strcmp(v, ref) == 0);
+  TORCH_CHECK(v == nullptr || v[0] == '\0' || is_ref || strcmp(v, prod) == 0,
+              "cached_step: ", name, " must be '", prod, "' or '", ref,
+              "', got '", v, "'");
+  return is_ref;
+}
 
 static RowCfg row_cfg() {
   RowCfg c;
-  const char* rk = getenv("DDLS_AMD_ROW_KERNELS");
-  c.thread = (rk != nullptr && strcmp(rk, "thread") == 0);
-  TORCH_CHECK(rk == nullptr || rk[0] == '\0' || c.thread
-              || strcmp(rk, "lanes") == 0,
-              "cached_step: DDLS_AMD_ROW_KERNELS must be 'thread' or "
-              "'lanes', got '", rk, "'");
+  c.reference = path_switch("DDLS_AMD_STEP_PATH", "production", "reference");
+  // Deprecated spellings.  Each of these switches used to bring back the
+  // launch sequence one generation older; those sequences are gone, and
+  // every one of them now selects the reference path, so an '=off' in an
+  // A/B script still compares production with something else.
+  c.reference |= path_switch("DDLS_AMD_ROW_KERNELS", "lanes", "thread");
+  for (const char* old : {"DDLS_AMD_STEP_FUSION", "DDLS_AMD_STEP_OVERLAP",
+                          "DDLS_AMD_STEP_MERGE", "DDLS_AMD_STEP_HEAD"})
+    c.reference |= path_switch(old, "on", "off");
   c.lanes = 0;
   const char* rl = getenv("DDLS_AMD_ROW_LANES");
   if (rl != nullptr && rl[0] != '\0') {
@@ -4151,30 +3365,6 @@ static RowCfg row_cfg() {
                 "cached_step: DDLS_AMD_ROW_LANES must be 8, 16 or 32, got '",
                 rl, "'");
   }
-  const char* sf = getenv("DDLS_AMD_STEP_FUSION");
-  const bool off = (sf != nullptr && strcmp(sf, "off") == 0);
-  TORCH_CHECK(sf == nullptr || sf[0] == '\0' || off || strcmp(sf, "on") == 0,
-              "cached_step: DDLS_AMD_STEP_FUSION must be 'on' or 'off', got '",
-              sf, "'");
-  c.fused = !off && !c.thread;
-  const char* so = getenv("DDLS_AMD_STEP_OVERLAP");
-  const bool ooff = (so != nullptr && strcmp(so, "off") == 0);
-  TORCH_CHECK(so == nullptr || so[0] == '\0' || ooff || strcmp(so, "on") == 0,
-              "cached_step: DDLS_AMD_STEP_OVERLAP must be 'on' or 'off', got '",
-              so, "'");
-  c.overlap = !ooff && c.fused;
-  const char* sm = getenv("DDLS_AMD_STEP_MERGE");
-  const bool moff = (sm != nullptr && strcmp(sm, "off") == 0);
-  TORCH_CHECK(sm == nullptr || sm[0] == '\0' || moff || strcmp(sm, "on") == 0,
-              "cached_step: DDLS_AMD_STEP_MERGE must be 'on' or 'off', got '",
-              sm, "'");
-  c.merge = !moff && c.overlap;
-  const char* sh = getenv("DDLS_AMD_STEP_HEAD");
-  const bool hoff = (sh != nullptr && strcmp(sh, "off") == 0);
-  TORCH_CHECK(sh == nullptr || sh[0] == '\0' || hoff || strcmp(sh, "on") == 0,
-              "cached_step: DDLS_AMD_STEP_HEAD must be 'on' or 'off', got '",
-              sh, "'");
-  c.head = !hoff && c.merge;
   return c;
 }
 
@@ -4197,13 +3387,9 @@ static RowCfg row_cfg() {
                            P, D);                                            \
     }                                                                        \
   } while (0)
-#define K_FWD_MLP1(L) (cs_fwd_mlp_lanes_kernel<1, L>)
-#define K_FWD_MLP2(L) (cs_fwd_mlp_lanes_kernel<2, L>)
-#define K_FWD_RED1(L) (cs_fwd_reduce_lanes_kernel<1, L>)
 #define K_FWD_RED2(L) (cs_fwd_reduce_lanes_kernel<2, L>)
 #define K_BWD_RED1(L) (cs_bwd_reduce_lanes_kernel<1, L>)
 #define K_BWD_RED2(L) (cs_bwd_reduce_lanes_kernel<2, L>)
-#define K_BWD_MLP2(L) (cs_bwd_mlp2_lanes_kernel<L>)
 #define K_FWD_COMB1_MLP2(L) (cs_fwd_comb1_mlp2_lanes_kernel<L>)
 #define K_BWD_SCAT2_MLP2(L) (cs_bwd_scat2_mlp2_lanes_kernel<L>)
 
@@ -4332,21 +3518,41 @@ static void fill_ptrs(CachedPtrs& P, CachedDims& D, RowCfg& R,
               "cached_step: wg_scratch too small");
 }
 
-// the forward launches; with SP/SD (cached_step_fwd_staged, overlap mode) the
-// first one carries the stage role in its block 0
+// the forward launches; with SP/SD (cached_step_fwd_staged, production only)
+// the first one carries the stage role in its block 0
 static void step_fwd_launches(const CachedPtrs& P, const CachedDims& D,
                               const RowCfg& R, const StagePtrs* SP,
                               const StageDims* SD) {
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  const int rows_b = (D.N + D.E + 255) / 256;
-  const int comb1_b = ((long)D.N * D.HID + 255) / 256;
-  const int comb2_b = ((long)D.N * D.OUT + 255) / 256;
-  if (R.thread) {
+  if (R.reference) {
+    const int rows_b = (D.N + D.E + 255) / 256;
+    const int comb1_b = ((long)D.N * D.HID + 255) / 256;
+    const int comb2_b = ((long)D.N * D.OUT + 255) / 256;
     hipLaunchKernelGGL(cs_fwd_mlp_kernel<1>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
     hipLaunchKernelGGL(cs_fwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
-  } else if (R.merge) {
+    hipLaunchKernelGGL(cs_fwd_combine_kernel<1>, dim3(comb1_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_mlp_kernel<2>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_combine_kernel<2>, dim3(comb2_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_pool_kernel, dim3(1), dim3(512), 0, stream,
+                       P, D);
+    int head_blocks = ((long)D.B * D.FC + 255) / 256;
+    if (head_blocks > 128) head_blocks = 128;
+    hipLaunchKernelGGL(cs_fwd_head_kernel, dim3(head_blocks), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_logits_kernel, dim3(D.B), dim3(512), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_fwd_loss_kernel, dim3((D.B + 31) / 32), dim3(256),
+                       0, stream, P, D);
+    return;
+  }
+  {
     // stage role (with a store) + round-1 modules + round-1 reduce module
     const int L_ = R.lanes ? R.lanes : 32;
     const int rpb_ = ROW_NT / L_;
@@ -4369,72 +3575,18 @@ static void step_fwd_launches(const CachedPtrs& P, const CachedDims& D,
         hipLaunchKernelGGL(cs_fwd_stage_mlp1_red1_lanes_kernel<32>, grid,
                            dim3(ROW_NT), 0, stream, P, D, sp, sd, stage);
     }
-  } else {
-    if (SP != nullptr) {
-      const int L_ = R.lanes ? R.lanes : 16;
-      const int rpb_ = ROW_NT / L_;
-      const dim3 grid(1 + (D.N + rpb_ - 1) / rpb_ + (D.E + rpb_ - 1) / rpb_);
-      if (L_ == 8)
-        hipLaunchKernelGGL(cs_fwd_stage_mlp1_lanes_kernel<8>, grid,
-                           dim3(ROW_NT), 0, stream, P, D, *SP, *SD);
-      else if (L_ == 16)
-        hipLaunchKernelGGL(cs_fwd_stage_mlp1_lanes_kernel<16>, grid,
-                           dim3(ROW_NT), 0, stream, P, D, *SP, *SD);
-      else
-        hipLaunchKernelGGL(cs_fwd_stage_mlp1_lanes_kernel<32>, grid,
-                           dim3(ROW_NT), 0, stream, P, D, *SP, *SD);
-    } else {
-      LAUNCH_ROWS(K_FWD_MLP1, 16, D.N, D.E);
-    }
-    LAUNCH_ROWS(K_FWD_RED1, 32, D.E, D.N);
   }
-  if (!R.fused)
-    hipLaunchKernelGGL(cs_fwd_combine_kernel<1>, dim3(comb1_b), dim3(256), 0,
+  LAUNCH_ROWS(K_FWD_COMB1_MLP2, 16, D.N, D.E);
+  LAUNCH_ROWS(K_FWD_RED2, 16, D.E, D.N);
+  // h2 and the per-model means, one block per model; then the whole
+  // per-sample chain (final rows, head, loss, head backward) in one launch,
+  // one sample a block: cached_step_bwd starts at the pool grads
+  if (D.M > 0)
+    hipLaunchKernelGGL(cs_fwd_comb2_pool_kernel, dim3(D.M), dim3(256), 0,
                        stream, P, D);
-  if (R.thread) {
-    hipLaunchKernelGGL(cs_fwd_mlp_kernel<2>, dim3(rows_b), dim3(256), 0,
-                       stream, P, D);
-    hipLaunchKernelGGL(cs_fwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
-                       stream, P, D);
-  } else {
-    if (R.fused)
-      LAUNCH_ROWS(K_FWD_COMB1_MLP2, 16, D.N, D.E);
-    else
-      LAUNCH_ROWS(K_FWD_MLP2, 16, D.N, D.E);
-    LAUNCH_ROWS(K_FWD_RED2, 16, D.E, D.N);
-  }
-  if (R.fused) {
-    // h2 and the per-model means, one block per model; then the whole
-    // per-sample chain (final rows, head, loss, head backward) in one
-    // launch: cached_step_bwd starts at cs_bwd_pool
-    if (D.M > 0)
-      hipLaunchKernelGGL(cs_fwd_comb2_pool_kernel, dim3(D.M), dim3(256), 0,
-                         stream, P, D);
-    // one sample a block (cs_head2) or four (cs_head, the oracle)
-    const int hb = R.head ? (D.B < HD2_MAXB ? D.B : HD2_MAXB)
-                          : (D.B < 32 ? D.B : 32);
-    if (hb > 0) {
-      if (R.head)
-        hipLaunchKernelGGL(cs_head2_kernel, dim3(hb), dim3(256), 0, stream,
-                           P, D);
-      else
-        hipLaunchKernelGGL(cs_head_kernel, dim3(hb), dim3(256), 0, stream,
-                           P, D);
-    }
-    return;
-  }
-  hipLaunchKernelGGL(cs_fwd_combine_kernel<2>, dim3(comb2_b), dim3(256), 0,
-                     stream, P, D);
-  hipLaunchKernelGGL(cs_fwd_pool_kernel, dim3(1), dim3(512), 0, stream,
-                     P, D);
-  int head_blocks = ((long)D.B * D.FC + 255) / 256;
-  if (head_blocks > 128) head_blocks = 128;
-  hipLaunchKernelGGL(cs_fwd_head_kernel, dim3(head_blocks), dim3(256), 0,
-                     stream, P, D);
-  hipLaunchKernelGGL(cs_fwd_logits_kernel, dim3(D.B), dim3(512), 0,
-                     stream, P, D);
-  hipLaunchKernelGGL(cs_fwd_loss_kernel, dim3((D.B + 31) / 32), dim3(256),
-                     0, stream, P, D);
+  const int hb = D.B < HD2_MAXB ? D.B : HD2_MAXB;
+  if (hb > 0)
+    hipLaunchKernelGGL(cs_head2_kernel, dim3(hb), dim3(256), 0, stream, P, D);
 }
 
 void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
@@ -4446,9 +3598,10 @@ void cached_step_fwd(std::vector<torch::Tensor> T, std::vector<double> fs) {
 }
 
 // cached_step_fwd with the minibatch gathered from the device batch store by
-// block 0 of the first launch (overlap mode only: the caller launches
-// cached_stage itself otherwise).  store / perm / cursor / err / dims are
-// cached_stage's arguments; the destinations are T's own staged inputs.
+// block 0 of the first launch (production path only: on the reference path
+// the caller launches cached_stage itself).  store / perm / cursor / err /
+// dims are cached_stage's arguments; the destinations are T's own staged
+// inputs.
 void cached_step_fwd_staged(std::vector<torch::Tensor> T,
                             std::vector<double> fs,
                             std::vector<torch::Tensor> store,
@@ -4459,8 +3612,8 @@ void cached_step_fwd_staged(std::vector<torch::Tensor> T,
   CachedDims D;
   RowCfg R;
   fill_ptrs(P, D, R, T, fs);
-  TORCH_CHECK(R.overlap, "cached_step_fwd_staged: needs the lane-parallel "
-              "fused launches with DDLS_AMD_STEP_OVERLAP on");
+  TORCH_CHECK(!R.reference, "cached_step_fwd_staged: production path only "
+              "(DDLS_AMD_STEP_PATH=reference stages with cached_stage)");
   StagePtrs SP;
   StageDims SD;
   cs_stage_args(SP, SD, "cached_step_fwd_staged", store,
@@ -4472,13 +3625,13 @@ void cached_step_fwd_staged(std::vector<torch::Tensor> T,
 
 // defer_reduce: leave the row jobs' partial sums in wg_scratch for the folded
 // optimiser tail (flat_sumsq_adam_folded), which then forms flat_g's row-job
-// segments itself.  Ignored unless the merge switch is on and the row jobs
-// are split (not with DDLS_AMD_WGRAD_MFMA=1); cached_step_reduce_deferred()
-// tells the caller.  Default: flat_g is complete when this returns.
+// segments itself.  Ignored on the reference path and when the row jobs are
+// not split (DDLS_AMD_WGRAD_MFMA=1); cached_step_reduce_deferred() tells the
+// caller.  Default: flat_g is complete when this returns.
 bool cached_step_reduce_deferred(bool defer_reduce) {
   const char* wm = getenv("DDLS_AMD_WGRAD_MFMA");
   const bool mfma = (wm != nullptr && wm[0] == '1');
-  return defer_reduce && row_cfg().merge && !mfma;
+  return defer_reduce && !row_cfg().reference && !mfma;
 }
 
 // The row jobs' gradient segments for the folded tail: for each of the 24
@@ -4516,59 +3669,57 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs,
   RowCfg R;
   fill_ptrs(P, D, R, T, fs);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  // cs_bwd_pool keeps the minibatch's model ids in a fixed LDS array
+  // the pool kernels keep the minibatch's model ids in a fixed LDS array
   TORCH_CHECK(D.B <= 1024 && D.B <= SG_MAXB,
               "cached_step: minibatch larger than 1024");
-  int hb = D.B < 32 ? D.B : 32;
-  const int rows_b = (D.N + D.E + 255) / 256;
-  const int scat_b = ((long)(D.N + D.E) * D.H + 255) / 256;
-  if (!R.fused)
+  const int nsplit = D.wgrad_mfma ? 1 : WSPLIT;
+  if (R.reference) {
+    const int hb = D.B < 32 ? D.B : 32;
+    const int rows_b = (D.N + D.E + 255) / 256;
+    const int scat_b = ((long)(D.N + D.E) * D.H + 255) / 256;
     hipLaunchKernelGGL(cs_bwd_head_kernel, dim3(hb), dim3(256), 0, stream,
                        P, D);
-  if (R.head) {
-    // the same roles in shorter blocks; its 16-byte loads need these rows
-    // aligned (every scratch tensor is an allocation of its own)
-    for (const float* q : {(const float*)P.fin, (const float*)P.gfinal,
-                           (const float*)P.gh1p, (const float*)P.gh1v,
-                           (const float*)P.h1p, (const float*)P.h1v})
-      TORCH_CHECK(reinterpret_cast<uintptr_t>(q) % 16 == 0,
-                  "cached_step: head scratch tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(cs_bwd_pool_wfc2_kernel, dim3(D.M + 1 + WFC2_NFC),
-                       dim3(256), 0, stream, P, D);
-  } else if (R.overlap)
-    // one pool block per model + the graph-module block + the FC-column
-    // blocks, which cs_bwd_w below then does not launch
-    hipLaunchKernelGGL(cs_bwd_pool_wfc_kernel, dim3(D.M + 1 + WFC_NFC),
-                       dim3(256), 0, stream, P, D);
-  else
     hipLaunchKernelGGL(cs_bwd_pool_kernel, dim3(1), dim3(512), 0, stream,
                        P, D);
-  if (R.thread)
     hipLaunchKernelGGL(cs_bwd_reduce_kernel<2>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
-  else
-    LAUNCH_ROWS(K_BWD_RED2, 16, D.E, D.N);
-  if (!R.fused)
     hipLaunchKernelGGL(cs_bwd_scatter_kernel<2>, dim3(scat_b), dim3(256), 0,
                        stream, P, D);
-  if (R.thread) {
     hipLaunchKernelGGL(cs_bwd_mlp2_kernel, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
     hipLaunchKernelGGL(cs_bwd_reduce_kernel<1>, dim3(rows_b), dim3(256), 0,
                        stream, P, D);
-  } else {
-    if (R.fused)
-      LAUNCH_ROWS(K_BWD_SCAT2_MLP2, 16, D.N, D.E);
-    else
-      LAUNCH_ROWS(K_BWD_MLP2, 16, D.N, D.E);
-    LAUNCH_ROWS(K_BWD_RED1, 32, D.E, D.N);
+    hipLaunchKernelGGL(cs_bwd_scatter_kernel<1>, dim3(scat_b), dim3(256), 0,
+                       stream, P, D);
+    hipLaunchKernelGGL(cs_bwd_gu1_kernel, dim3(rows_b), dim3(256), 0, stream,
+                       P, D);
+    // 6 row jobs x nsplit, the graph-module block, 16 FC-column blocks
+    hipLaunchKernelGGL(cs_bwd_w_kernel, dim3(6 * nsplit + 1 + 16), dim3(256),
+                       0, stream, P, D);
+    if (nsplit > 1)
+      hipLaunchKernelGGL(cs_bwd_w_reduce_kernel, dim3(6), dim3(256), 0,
+                         stream, P, D);
+    return;
   }
-  const int nsplit = D.wgrad_mfma ? 1 : WSPLIT;
-  if (R.merge && nsplit > 1 && D.B > 0) {
-    // the scatter's row blocks and statistics block, then the 6 x WSPLIT
-    // row-job blocks, in one launch
-    const int sg_b = (D.N + SG_RPB - 1) / SG_RPB + (D.E + SG_RPB - 1) / SG_RPB
-                     + 1;
+  // one pool block per model + the graph-module block + the FC-column blocks
+  // (the B-row weight grads, which cs_bwd_w below then does not launch); its
+  // 16-byte loads need these rows aligned (every scratch tensor is an
+  // allocation of its own)
+  for (const float* q : {(const float*)P.fin, (const float*)P.gfinal,
+                         (const float*)P.gh1p, (const float*)P.gh1v,
+                         (const float*)P.h1p, (const float*)P.h1v})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(q) % 16 == 0,
+                "cached_step: head scratch tensors must be 16-byte aligned");
+  hipLaunchKernelGGL(cs_bwd_pool_wfc2_kernel, dim3(D.M + 1 + WFC2_NFC),
+                     dim3(256), 0, stream, P, D);
+  LAUNCH_ROWS(K_BWD_RED2, 16, D.E, D.N);
+  LAUNCH_ROWS(K_BWD_SCAT2_MLP2, 16, D.N, D.E);
+  LAUNCH_ROWS(K_BWD_RED1, 32, D.E, D.N);
+  // row blocks, then the loss-statistics block
+  const int sg_b = (D.N + SG_RPB - 1) / SG_RPB + (D.E + SG_RPB - 1) / SG_RPB
+                   + 1;
+  if (nsplit > 1 && D.B > 0) {
+    // the scatter's blocks, then the 6 x WSPLIT row-job blocks, in one launch
     hipLaunchKernelGGL(cs_bwd_scat1_gu1_w_kernel, dim3(sg_b + 6 * WSPLIT),
                        dim3(ROW_NT), 0, stream, P, D);
     if (!defer_reduce)
@@ -4576,36 +3727,14 @@ void cached_step_bwd(std::vector<torch::Tensor> T, std::vector<double> fs,
                          stream, P, D);
     return;
   }
-  if (R.fused) {
-    // row blocks, then the loss-statistics block
-    const int sg_b = (D.N + SG_RPB - 1) / SG_RPB + (D.E + SG_RPB - 1) / SG_RPB
-                     + 1;
-    if (D.B > 0)
-      hipLaunchKernelGGL(cs_bwd_scat1_gu1_kernel, dim3(sg_b), dim3(ROW_NT),
-                         0, stream, P, D);
-  } else {
-    hipLaunchKernelGGL(cs_bwd_scatter_kernel<1>, dim3(scat_b), dim3(256), 0,
+  // no row-split partials (DDLS_AMD_WGRAD_MFMA=1): the scatter and the row
+  // jobs as launches of their own
+  if (D.B > 0)
+    hipLaunchKernelGGL(cs_bwd_scat1_gu1_kernel, dim3(sg_b), dim3(ROW_NT), 0,
                        stream, P, D);
-  }
-  if (R.fused) {
-    // gu_z1 / gu_e1 came out of the scatter launch above
-  } else if (R.thread) {
-    hipLaunchKernelGGL(cs_bwd_gu1_kernel, dim3(rows_b), dim3(256), 0, stream,
+  hipLaunchKernelGGL(cs_bwd_w_kernel, dim3(6 * nsplit), dim3(256), 0, stream,
+                     P, D);
+  if (nsplit > 1 && !defer_reduce)
+    hipLaunchKernelGGL(cs_bwd_w_reduce_kernel, dim3(6), dim3(256), 0, stream,
                        P, D);
-  } else {
-    const int gu1_b =
-        (int)(((long)D.N * KF0 + (long)D.E * KFE + ROW_NT - 1) / ROW_NT);
-    if (gu1_b > 0)
-      hipLaunchKernelGGL(cs_bwd_gu1_lanes_kernel, dim3(gu1_b), dim3(ROW_NT),
-                         0, stream, P, D);
-  }
-  // 6 row jobs x nsplit, the graph-module block, 16 FC-column blocks; in
-  // overlap mode the 17 B-row blocks ran in cs_bwd_pool_wfc above, and with
-  // the row-job grid their paths are never entered
-  hipLaunchKernelGGL(cs_bwd_w_kernel,
-                     dim3(6 * nsplit + (R.overlap ? 0 : 1 + 16)), dim3(256),
-                     0, stream, P, D);
-  if (nsplit > 1 && !(defer_reduce && R.merge))
-    hipLaunchKernelGGL(cs_bwd_w_reduce_kernel, dim3(6), dim3(256), 0,
-                       stream, P, D);
 }

@@ -35,39 +35,40 @@ from ..parallel import all_reduce_gradients, is_distributed
 from .rollout import CompactObs
 
 
+# (name, production value, reference value) of cached_step.hip's path switch
+# and of its deprecated spellings: each of those used to bring back the launch
+# sequence one generation older, and every one now selects the reference path
+_STEP_PATH_SWITCHES = (
+    ("DDLS_AMD_STEP_PATH", "production", "reference"),
+    ("DDLS_AMD_ROW_KERNELS", "lanes", "thread"),
+    ("DDLS_AMD_STEP_FUSION", "on", "off"),
+    ("DDLS_AMD_STEP_OVERLAP", "on", "off"),
+    ("DDLS_AMD_STEP_MERGE", "on", "off"),
+    ("DDLS_AMD_STEP_HEAD", "on", "off"))
+
+
+def step_reference_path() -> bool:
+    """Mirror of cached_step.hip's row_cfg() (read per call): True on the
+    reference path, the thread-per-row and separate kernels; False on the
+    production path, where the stage role rides in the step's first forward
+    launch and the row-split weight-grad reduce may be left to the folded
+    optimiser tail."""
+    ref = False
+    for name, prod, refv in _STEP_PATH_SWITCHES:
+        v = os.environ.get(name, "")
+        if v not in ("", prod, refv):
+            raise RuntimeError(
+                f"{name} must be '{prod}' or '{refv}', got '{v}'")
+        ref = ref or v == refv
+    return ref
+
+
 def step_fusion_enabled() -> bool:
-    """Mirror of cached_step.hip's launch switch for the optimiser tail:
-    DDLS_AMD_STEP_FUSION=off, or the thread-per-row oracle
-    (DDLS_AMD_ROW_KERNELS=thread), keeps the previous launch sequence."""
-    v = os.environ.get("DDLS_AMD_STEP_FUSION", "")
-    if v not in ("", "on", "off"):
-        raise RuntimeError(
-            f"DDLS_AMD_STEP_FUSION must be 'on' or 'off', got '{v}'")
-    return (v != "off"
-            and os.environ.get("DDLS_AMD_ROW_KERNELS", "") != "thread")
+    """Deprecated: ``not step_reference_path()``."""
+    return not step_reference_path()
 
 
-def step_overlap_enabled() -> bool:
-    """Mirror of cached_step.hip's DDLS_AMD_STEP_OVERLAP switch (default on):
-    the stage role rides in the step's first forward launch.  It needs the
-    fused launches, so whatever turns those off turns this off too."""
-    v = os.environ.get("DDLS_AMD_STEP_OVERLAP", "")
-    if v not in ("", "on", "off"):
-        raise RuntimeError(
-            f"DDLS_AMD_STEP_OVERLAP must be 'on' or 'off', got '{v}'")
-    return v != "off" and step_fusion_enabled()
-
-
-def step_merge_enabled() -> bool:
-    """Mirror of cached_step.hip's DDLS_AMD_STEP_MERGE switch (default on):
-    the row-split weight-grad reduce may be left to the folded optimiser
-    tail.  It needs the overlap launches, so whatever turns those off turns
-    this off too."""
-    v = os.environ.get("DDLS_AMD_STEP_MERGE", "")
-    if v not in ("", "on", "off"):
-        raise RuntimeError(
-            f"DDLS_AMD_STEP_MERGE must be 'on' or 'off', got '{v}'")
-    return v != "off" and step_overlap_enabled()
+step_overlap_enabled = step_merge_enabled = step_fusion_enabled
 
 
 class _PPOLossFn(torch.autograd.Function):
@@ -244,12 +245,12 @@ class _FusedCachedEngine:
 
     def run(self, store=None, defer_reduce=False):
         """One fwd+bwd.  With a ``DeviceBatchStore`` the minibatch is gathered
-        from it first: inside the first forward launch when the overlap
-        switch is on, by the stage kernel's own launch otherwise.  With
+        from it first: inside the first forward launch on the production
+        path, by the stage kernel's own launch on the reference path.  With
         ``defer_reduce`` the row-split weight-grad partials stay in the
         scratch buffer and ``flat_g`` is complete only after the folded
         optimiser tail; the default leaves a complete ``flat_g``."""
-        if store is not None and step_overlap_enabled():
+        if store is not None and not step_reference_path():
             self.ext.cached_step_fwd_staged(
                 self.scratch, self.fscal, store.tensors(), store.perm,
                 store.cursor, store.err, [store.n_rows, store.n_mb])
@@ -776,7 +777,7 @@ class CapturedSGDStep:
 
     # ------------------------------------------------------------------
     _fused_cached = None
-    # the step is captured whole with the merge switch on: _body_fwd_bwd
+    # the step is captured whole on the production path: _body_fwd_bwd
     # defers the row-split weight-grad reduce and _body_opt runs the folded
     # tail.  Decided in _capture; never with a distributed (split) capture,
     # whose all-reduce needs a complete flat_g in between.
@@ -787,8 +788,8 @@ class CapturedSGDStep:
         if self._fused_cached is not None:
             # fully-fused path, grads straight into flat_g.  With a device
             # batch store the gather of this minibatch's rows rides in the
-            # first forward launch (DDLS_AMD_STEP_OVERLAP=off: the stage
-            # kernel's own launch in front, as below)
+            # first forward launch (reference path: the stage kernel's own
+            # launch in front, as below)
             # (_fold_tail: cs_bwd_w_reduce's work is done by the tail)
             self._fused_cached.run(self.store, defer_reduce=self._fold_tail)
             return
@@ -898,17 +899,11 @@ class CapturedSGDStep:
                     self._fused_cached.scratch[-1], segs, nsplit, stride,
                     *hyper)
                 return
-            if step_fusion_enabled():
-                # two launches: block partials of the norm (+ the step
-                # count), then their fixed-order sum + clip + Adam
-                self._ext.flat_sumsq_adam(
-                    self.flat_p, self.flat_g, self.flat_m, self.flat_v,
-                    self.step_t, self.normsq, self.normsq_partials, *hyper)
-                return
-            self._ext.flat_sumsq(self.flat_g, self.normsq)
-            self._ext.flat_adam(self.flat_p, self.flat_g, self.flat_m,
-                                self.flat_v, self.step_t, self.normsq,
-                                *hyper)
+            # two launches: block partials of the norm (+ the step count),
+            # then their fixed-order sum + clip + Adam
+            self._ext.flat_sumsq_adam(
+                self.flat_p, self.flat_g, self.flat_m, self.flat_v,
+                self.step_t, self.normsq, self.normsq_partials, *hyper)
             return
         if self.cfg.grad_clip is not None:
             torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
@@ -1014,7 +1009,7 @@ class CapturedSGDStep:
                                                         self.models_batch)
             self._fold_tail = bool(
                 self._fused_cached is not None and not split
-                and step_merge_enabled()
+                and not step_reference_path()
                 and hasattr(self._ext, "flat_sumsq_adam_folded")
                 and self._ext.cached_step_reduce_deferred(True))
             # warmup (required before capture) runs REAL steps; snapshot the

@@ -21,6 +21,16 @@ sets it for all of them (every case below also runs at 8, 16 and 32).  At
   straddle      N=24 E=25   (N+E) mod 16 == 1, N no multiple of 16
   bench         the benchmark's own model set (data/small_graphs), B=128
 All but the last contain source nodes without in-edges (f = 0 self rows).
+
+Since the path consolidation the step holds two launch sequences only, and
+the switch this file sets is a deprecated spelling: ``thread`` / ``off``
+selects the reference path (``DDLS_AMD_STEP_PATH=reference``, the
+thread-per-row and separate kernels), whatever generation it used to bring
+back.  Every comparison below is therefore production against that reference
+path (two ``off`` spellings against each other compare the reference path
+with itself), and the kernels of the generations in between, named above,
+no longer exist.  tests/test_step_paths.py holds the same cases in the new
+spelling; this file stays until the old names are retired.
 """
 import os
 import re

@@ -24,6 +24,16 @@ Tail: the new binding against ``flat_sumsq`` + ``flat_adam`` on synthetic
 flat buffers: one block, the policy's size (138 blocks, a partial last one),
 and a size past the 512-block cap where the grid-stride loops take a second
 trip.
+
+Since the path consolidation the step holds two launch sequences only, and
+the switch this file sets is a deprecated spelling: ``thread`` / ``off``
+selects the reference path (``DDLS_AMD_STEP_PATH=reference``, the
+thread-per-row and separate kernels), whatever generation it used to bring
+back.  Every comparison below is therefore production against that reference
+path (two ``off`` spellings against each other compare the reference path
+with itself), and the kernels of the generations in between, named above,
+no longer exist.  tests/test_step_paths.py holds the same cases in the new
+spelling; this file stays until the old names are retired.
 """
 import os
 

@@ -29,6 +29,16 @@ one, one plus two rows) and 257 (two super-tiles plus one row) cross each of
 those boundaries.  For the head kernel B <= 128 is one sample a block (fewer
 samples than the 128-block cap), B = 130 two samples in the first blocks and
 empty last blocks, B = 257 three in a block and a short last block.
+
+Since the path consolidation the step holds two launch sequences only, and
+the switch this file sets is a deprecated spelling: ``thread`` / ``off``
+selects the reference path (``DDLS_AMD_STEP_PATH=reference``, the
+thread-per-row and separate kernels), whatever generation it used to bring
+back.  Every comparison below is therefore production against that reference
+path (two ``off`` spellings against each other compare the reference path
+with itself), and the kernels of the generations in between, named above,
+no longer exist.  tests/test_step_paths.py holds the same cases in the new
+spelling; this file stays until the old names are retired.
 """
 import os
 

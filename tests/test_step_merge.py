@@ -27,6 +27,16 @@ order of the C_* enum; ``C_STATS`` alone keeps its 1e-4 tolerance.
 A merged first-launch block holds 256/L rows of one class (edge rows, then
 self rows), L = 32 by default; every case also runs at 8 and 16 lanes per
 row, because the merged staging depends on the rows per block.
+
+Since the path consolidation the step holds two launch sequences only, and
+the switch this file sets is a deprecated spelling: ``thread`` / ``off``
+selects the reference path (``DDLS_AMD_STEP_PATH=reference``, the
+thread-per-row and separate kernels), whatever generation it used to bring
+back.  Every comparison below is therefore production against that reference
+path (two ``off`` spellings against each other compare the reference path
+with itself), and the kernels of the generations in between, named above,
+no longer exist.  tests/test_step_paths.py holds the same cases in the new
+spelling; this file stays until the old names are retired.
 """
 import os
 

@@ -22,6 +22,16 @@ super-tile in 32-row tiles:
   B = 130  a super-tile plus a 2-row tail
   B = 160  a super-tile plus one full tile
   B = 257  two super-tiles plus one row
+
+Since the path consolidation the step holds two launch sequences only, and
+the switch this file sets is a deprecated spelling: ``thread`` / ``off``
+selects the reference path (``DDLS_AMD_STEP_PATH=reference``, the
+thread-per-row and separate kernels), whatever generation it used to bring
+back.  Every comparison below is therefore production against that reference
+path (two ``off`` spellings against each other compare the reference path
+with itself), and the kernels of the generations in between, named above,
+no longer exist.  tests/test_step_paths.py holds the same cases in the new
+spelling; this file stays until the old names are retired.
 """
 import os
 
