@@ -577,3 +577,42 @@ class GNNPolicy(nn.Module):
             obs["edges_dst"], obs["node_split"], obs["edge_split"])
         return self.forward_flat(batch, obs["graph_features"],
                                  obs["action_mask"])
+
+
+TRUNK_NUMEL = 4146      # parameters of the tuned GNN (gnn_trunk.hip, GT_NP)
+
+
+@torch.no_grad()
+def gnn_trunk_population(pop: torch.Tensor, batch: GraphBatch,
+                         offset: int = 0) -> torch.Tensor:
+    """Per-graph mean node embeddings ``[P, G, 16]`` of ``P`` tuned GNNs on
+    one ``batch``: member ``m``'s trunk is ``pop[m, offset : offset + 4146]``
+    in ``gnn.parameters()`` order (``offset = 0`` for a flat ``GNNPolicy``).
+    On a GPU this is one launch of ``gt_pop_fwd_kernel``
+    (ops/hip/gnn_trunk.hip); anything else is the plain chain, member by
+    member, which is also the kernel's oracle.  No gradient."""
+    if pop.dim() != 2 or pop.shape[0] < 1 or offset < 0 \
+            or offset + TRUNK_NUMEL > pop.shape[1]:
+        raise ValueError(
+            "gnn_trunk_population: pop must be [P >= 1, n] with the tuned "
+            f"trunk's {TRUNK_NUMEL} parameters at [offset, offset + "
+            f"{TRUNK_NUMEL}); got {tuple(pop.shape)}, offset {offset}")
+    if (batch.z.is_cuda
+            and os.environ.get("DDLS_AMD_DISABLE_HIP", "0") != "1"):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        return ext.gnn_trunk_population_fwd(
+            batch.z.detach().float().contiguous(),
+            batch.e.detach().float().contiguous(), list(batch.trunk_plan()),
+            pop.detach().float().contiguous(), int(offset))
+    gnn = GNN(dict(DEFAULT_GNN_CONFIG)).to(batch.z.device, batch.z.dtype)
+    params = list(gnn.parameters())
+    assert sum(p.numel() for p in params) == TRUNK_NUMEL
+    out = []
+    for m in range(pop.shape[0]):
+        off = offset
+        for p in params:
+            p.copy_(pop[m, off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        out.append(graph_mean(gnn(batch), batch))
+    return torch.stack(out).contiguous()

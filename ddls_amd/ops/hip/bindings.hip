@@ -125,6 +125,9 @@ std::vector<torch::Tensor> gnn_trunk_bwd(torch::Tensor gemb,
                                          torch::Tensor workspace,
                                          std::vector<torch::Tensor> plan,
                                          std::vector<torch::Tensor> params);
+torch::Tensor gnn_trunk_population_fwd(torch::Tensor z, torch::Tensor e,
+                                       std::vector<torch::Tensor> plan,
+                                       torch::Tensor pop, int64_t off);
 void per_ingest(torch::Tensor tree_sum, torch::Tensor tree_min,
                 torch::Tensor max_prio, int64_t start, int64_t count,
                 int64_t capacity, double alpha);
@@ -229,6 +232,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gnn_trunk_bwd", &gnn_trunk_bwd,
           "analytic GNN trunk backward into the 24 gnn.parameters() tensors "
           "(row kernel + MFMA weight-grad tiles)");
+    m.def("gnn_trunk_population_fwd", &gnn_trunk_population_fwd,
+          "GNN trunk forward of P population members in one launch, one "
+          "workgroup per (graph, member), weights read from pop[m, off:]; "
+          "returns model_emb [P, G, 16]");
     m.def("per_ingest", &per_ingest,
           "prioritized replay: new slots enter the sum/min trees at "
           "max_prio^alpha");

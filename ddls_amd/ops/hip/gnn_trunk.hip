@@ -58,6 +58,7 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -662,6 +663,260 @@ gt_bwd_wgrad_kernel(GtParams w, GtWs ws, GtBs bs,
                     G + GtL2::r_lnb);
 }
 
+// ---------------------------------------------------------------------------
+// population forward (ES): P members x G graphs in one launch, forward only
+//
+//   gt_pop_fwd_kernel    grid = (G, P), one workgroup per (graph, member).
+//                        Member m's 4146 trunk weights are the contiguous
+//                        range pop[m, off : off + 4146], already in GtLay
+//                        order: one pass stages them into LDS, the six W
+//                        matrices transposed as gt_stage_layer<L, true> does
+//                        (scalar loads: a row of pop is not 16-byte aligned).
+//                        A round is two phases instead of five:
+//                          A  per node / edge row, one 16-lane group:
+//                             LayerNorm -> Linear -> ReLU      -> hn, he
+//                          B  per destination node, OUT lanes: self message,
+//                             then in-edges ascending; gather, LayerNorm over
+//                             32, reduce Linear + ReLU, running sum -> z
+//                        xn / xe / mh / rs / r never reach memory.  The rows
+//                        between the phases (hn, he, z1; z2 takes z1's place)
+//                        are Ng * 80 + Eg * 16 floats: in LDS when that fits
+//                        GT_POP_ROWS, else in the (member, graph) slab of a
+//                        global scratch tensor.
+//
+// The arithmetic is gt_fwd_kernel's, operation for operation: the same f64
+// sums in the same order, rounded to f32 where gt_fwd_kernel stores (xh, hn /
+// he, mh, r, z), so member m's output equals gnn_trunk_fwd on member m's
+// tensors bit for bit.
+#define GT_POP_ROWS 8192      // floats; 16.6 KB weights + 4 KB partials +
+                              // 32 KB rows < 160 KB / 3: LDS allows the 3
+                              // workgroups per CU that 80 VGPRs allow
+#define GT_POP_NODE (GT_HALF + 64)   // hn row + z1 row, floats per node
+
+// where element i of the flat GtLay range lands in LDS
+template <class L>
+__device__ __forceinline__ int gt_pop_dst(int i) {
+    if (i >= L::n_W && i < L::n_b) {
+        const int u = i - L::n_W;
+        return L::n_W + (u % L::FN) * GT_HALF + u / L::FN;
+    }
+    if (i >= L::e_W && i < L::e_b) {
+        const int u = i - L::e_W;
+        return L::e_W + (u % GT_FE) * GT_HALF + u / GT_FE;
+    }
+    if (i >= L::r_W && i < L::r_b) {
+        const int u = i - L::r_W;
+        return L::r_W + (u % GT_MSG) * L::OUT + u / GT_MSG;
+    }
+    return i;
+}
+
+// Phase A of one row by the 16 lanes of a group (all 16 active): lane j holds
+// x[j], x[16 + j], ...; every lane walks k = 0 .. K-1 over lane shuffles in
+// gt_ln_row's order, so the 16 lanes hold the same statistics; lane j then
+// owns xh[j], xh[16 + j], ... and output j (gt_lin_relu's sum).
+template <int K>
+__device__ __forceinline__ float gt_pop_row(const float* x, const float* lnw,
+                                            const float* lnb, const float* WT,
+                                            int j, float bias) {
+    constexpr int NV = (K + GT_HALF - 1) / GT_HALF;
+    float xr[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int k = i * GT_HALF + j;
+        xr[i] = k < K ? x[k] : 0.0f;
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        constexpr int KK = K < GT_HALF ? K : GT_HALF;
+#pragma unroll 8
+        for (int kk = 0; kk < KK; ++kk)
+            s += (double)__shfl(xr[i], kk, GT_HALF);
+    }
+    const double mean = s / K;
+    double v = 0.0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        constexpr int KK = K < GT_HALF ? K : GT_HALF;
+#pragma unroll 8
+        for (int kk = 0; kk < KK; ++kk) {
+            const double d = (double)__shfl(xr[i], kk, GT_HALF) - mean;
+            v = fma(d, d, v);
+        }
+    }
+    const double rstd = 1.0 / sqrt(v / K + GT_LN_EPS);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        xr[i] = (float)(((double)xr[i] - mean) * rstd);
+    double acc = (double)bias;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        constexpr int KK = K < GT_HALF ? K : GT_HALF;
+#pragma unroll 8
+        for (int kk = 0; kk < KK; ++kk) {
+            const int k = i * GT_HALF + kk;
+            const float xh = __shfl(xr[i], kk, GT_HALF);
+            const double y = fma((double)xh, (double)lnw[k], (double)lnb[k]);
+            acc = fma((double)WT[k * GT_HALF + j], y, acc);
+        }
+    }
+    return fmaxf((float)acc, 0.0f);
+}
+
+// One message through the reduce module, output j: a = hn[src], b = he[p]
+// for an edge message; the self message has zeros in b's place.  Phases 3 and
+// 4 of gt_round_fwd with nothing stored: the row is read three times (LDS, or
+// L1 on the scratch path) so that no loop needs it in registers.
+template <class L, bool EDGE>
+__device__ __forceinline__ float gt_pop_msg(const float* P, const float* a,
+                                            const float* b, int j) {
+    double s = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < GT_HALF; ++k) {
+        s += (double)a[k];
+        if (EDGE) s += (double)b[k];
+    }
+    const double mean = s / GT_MSG;
+    double var = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < GT_HALF; ++k) {
+        const double da = (double)a[k] - mean;
+        const double db = (EDGE ? (double)b[k] : 0.0) - mean;
+        var = fma(da, da, var);
+        var = fma(db, db, var);
+    }
+    const double rstd = 1.0 / sqrt(var / GT_MSG + GT_LN_EPS);
+    // mh[k] is rounded to f32 as gt_round_fwd stores it, then gt_lin_relu's
+    // sum over k = 0 .. 31: the hn half, then the he half
+    double acc = (double)P[L::r_b + j];
+#pragma unroll 4
+    for (int k = 0; k < GT_HALF; ++k) {
+        const float mh = (float)(((double)a[k] - mean) * rstd);
+        const double y = fma((double)mh, (double)P[L::r_lnw + k],
+                             (double)P[L::r_lnb + k]);
+        acc = fma((double)P[L::r_W + k * L::OUT + j], y, acc);
+    }
+#pragma unroll 4
+    for (int k = 0; k < GT_HALF; ++k) {
+        const float mh = (float)(((EDGE ? (double)b[k] : 0.0) - mean) * rstd);
+        const double y = fma((double)mh, (double)P[L::r_lnw + GT_HALF + k],
+                             (double)P[L::r_lnb + GT_HALF + k]);
+        acc = fma((double)P[L::r_W + (GT_HALF + k) * L::OUT + j], y, acc);
+    }
+    return fmaxf((float)acc, 0.0f);
+}
+
+// One MeanPool round of graph rows [n0, n1) / positions [e0, e1) over row
+// pointers (LDS or global alike).  x is the round's node input, row v at
+// x + (v - xbase) * FN; hn [Ng, 16], he [Eg, 16] and z [Ng, OUT] are indexed
+// from the graph's first node / position.
+template <class L>
+__device__ __forceinline__ void gt_pop_round(
+    const float* P, const float* x, int xbase, const float* __restrict__ e,
+    const GtPlan& pl, int n0, int n1, int e0, int e1, float* hn, float* he,
+    float* z) {
+    constexpr int FN = L::FN, OUT = L::OUT;
+    const int tid = threadIdx.x;
+    const int Ng = n1 - n0, Eg = e1 - e0;
+    // A: one 16-lane group per node row / edge row
+    {
+        const int j = tid % GT_HALF;
+        for (int row = tid / GT_HALF; row < Ng + Eg;
+             row += GT_BLOCK / GT_HALF) {
+            if (row < Ng) {
+                hn[row * GT_HALF + j] = gt_pop_row<FN>(
+                    x + (long)(n0 + row - xbase) * FN, P + L::n_lnw,
+                    P + L::n_lnb, P + L::n_W, j, P[L::n_b + j]);
+            } else {
+                const int q = row - Ng;
+                he[q * GT_HALF + j] = gt_pop_row<GT_FE>(
+                    e + (long)pl.eo[e0 + q] * GT_FE, P + L::e_lnw,
+                    P + L::e_lnb, P + L::e_W, j, P[L::e_b + j]);
+            }
+        }
+    }
+    __syncthreads();
+    // B: OUT lanes per destination node, lane j owns output j
+    {
+        const int j = tid % OUT;
+        for (int t = tid / OUT; t < Ng; t += GT_BLOCK / OUT) {
+            const int v = n0 + t;
+            const int pb = pl.indptr[v], pe = pl.indptr[v + 1];
+            float out = 0.0f;
+            if (pe > pb) {
+                double acc = (double)gt_pop_msg<L, false>(
+                    P, hn + t * GT_HALF, nullptr, j);
+                for (int p = pb; p < pe; ++p)
+                    acc += (double)gt_pop_msg<L, true>(
+                        P, hn + (pl.srcp[p] - n0) * GT_HALF,
+                        he + (p - e0) * GT_HALF, j);
+                out = (float)(acc / (double)(pe - pb + 1));
+            }
+            z[t * OUT + j] = out;
+        }
+    }
+    __syncthreads();
+}
+
+// both rounds over one set of row pointers; z2 takes z1's place (round 2
+// reads z1 in phase A only, and a barrier ends that phase)
+__device__ __forceinline__ const float* gt_pop_rounds(
+    const float* P, const float* __restrict__ z0, const float* __restrict__ e,
+    const GtPlan& pl, int n0, int n1, int e0, int e1, float* rows) {
+    float* hn = rows;
+    float* he = hn + (long)(n1 - n0) * GT_HALF;
+    float* zz = he + (long)(e1 - e0) * GT_HALF;
+    gt_pop_round<GtL1>(P, z0, 0, e, pl, n0, n1, e0, e1, hn, he, zz);
+    gt_pop_round<GtL2>(P, zz, n0, e, pl, n0, n1, e0, e1, hn, he, zz);
+    return zz;
+}
+
+__global__ void __launch_bounds__(GT_BLOCK)
+gt_pop_fwd_kernel(const float* __restrict__ z0,      // [N, 5]
+                  const float* __restrict__ e,       // [E, 2]
+                  GtPlan pl,
+                  const float* __restrict__ pop,     // [P, n], trunk at off
+                  long n, long off,
+                  float* __restrict__ scratch,       // [P, slab] or null
+                  long slab,                         // N * 80 + E * 16
+                  float* __restrict__ emb) {         // [P, G, 16]
+    __shared__ float P[GT_NP];
+    __shared__ __attribute__((aligned(16))) float R[GT_POP_ROWS];
+    __shared__ double part[GT_BLOCK / GT_HALF][GT_HALF];
+    const int g = blockIdx.x, m = blockIdx.y;
+    const float* w = pop + (long)m * n + off;
+    for (int i = threadIdx.x; i < GT_NP; i += GT_BLOCK)
+        P[i < GtL1::end ? gt_pop_dst<GtL1>(i) : gt_pop_dst<GtL2>(i)] = w[i];
+    __syncthreads();
+    const int n0 = pl.node_ptr[g], n1 = pl.node_ptr[g + 1];
+    const int e0 = pl.indptr[n0], e1 = pl.indptr[n1];
+    const long need = (long)(n1 - n0) * GT_POP_NODE + (long)(e1 - e0) * GT_HALF;
+    // one branch per address space, so each copy of the rounds is compiled
+    // for LDS or for global rows
+    const float* z2;
+    if (need <= GT_POP_ROWS)
+        z2 = gt_pop_rounds(P, z0, e, pl, n0, n1, e0, e1, R);
+    else
+        z2 = gt_pop_rounds(P, z0, e, pl, n0, n1, e0, e1,
+                           scratch + (long)m * slab + (long)n0 * GT_POP_NODE
+                               + (long)e0 * GT_HALF);
+    // graph mean: 32 row groups x 16 features, partials summed in order
+    const int j = threadIdx.x % GT_HALF, grp = threadIdx.x / GT_HALF;
+    double acc = 0.0;
+    for (int t = grp; t < n1 - n0; t += GT_BLOCK / GT_HALF)
+        acc += (double)z2[t * GT_HALF + j];
+    part[grp][j] = acc;
+    __syncthreads();
+    if (threadIdx.x < GT_HALF) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < GT_BLOCK / GT_HALF; ++q) s += part[q][threadIdx.x];
+        emb[((long)m * gridDim.x + g) * GT_HALF + threadIdx.x] =
+            n1 > n0 ? (float)(s / (double)(n1 - n0)) : 0.0f;
+    }
+}
+
 #ifdef __HIP_DEVICE_COMPILE__
 #pragma clang attribute pop
 #endif
@@ -832,4 +1087,58 @@ std::vector<torch::Tensor> gnn_trunk_bwd(torch::Tensor gemb,
         off += p.numel();
     }
     return grads;
+}
+
+// model_emb [P, G, 16] of P population members in one launch: member m's
+// trunk is pop[m, off : off + 4146] (gnn.parameters() order).  Forward only,
+// no workspace.  Scratch is allocated only when some graph's rows exceed
+// GT_POP_ROWS; finding that out reads node_ptr / indptr back (one sync), and
+// only when the whole batch is larger than the budget.
+torch::Tensor gnn_trunk_population_fwd(torch::Tensor z, torch::Tensor e,
+                                       std::vector<torch::Tensor> plan,
+                                       torch::Tensor pop, int64_t off) {
+    int64_t N, E, G;
+    gt_check_batch(z, e, &N, &E);
+    const GtPlan pl = gt_check_plan(plan, N, E, &G);
+    TORCH_CHECK(pop.is_cuda() && pop.device() == z.device()
+                && pop.scalar_type() == torch::kFloat32 && pop.dim() == 2
+                && pop.is_contiguous(),
+                "gnn_trunk population: pop must be a contiguous float32 "
+                "[P, n] tensor on the batch's device");
+    const int64_t P = pop.size(0), n = pop.size(1);
+    TORCH_CHECK(P >= 1 && P <= 65535 && G <= 0x7fffffff,
+                "gnn_trunk population: needs 1 <= P <= 65535 members, got ",
+                P);
+    TORCH_CHECK(off >= 0 && off + GT_NP <= n,
+                "gnn_trunk population: the trunk's ", (int)GT_NP,
+                " parameters at offset ", off, " do not fit a row of ", n,
+                " (the kernels serve the tuned GNN shape only)");
+    const int64_t slab = N * GT_POP_NODE + E * GT_HALF;
+    torch::Tensor scratch;
+    if (slab > GT_POP_ROWS) {
+        const auto np = plan[6].cpu(), ip = plan[3].cpu();
+        const int* npp = np.data_ptr<int>();
+        const int* ipp = ip.data_ptr<int>();
+        int64_t worst = 0;
+        for (int64_t g = 0; g < G; ++g) {
+            TORCH_CHECK(npp[g] >= 0 && npp[g] <= npp[g + 1]
+                        && npp[g + 1] <= N,
+                        "gnn_trunk population: node_ptr is not a prefix "
+                        "over [0, N]");
+            worst = std::max<int64_t>(
+                worst, (int64_t)(npp[g + 1] - npp[g]) * GT_POP_NODE
+                           + (int64_t)(ipp[npp[g + 1]] - ipp[npp[g]])
+                                 * GT_HALF);
+        }
+        if (worst > GT_POP_ROWS) scratch = torch::empty({P * slab}, z.options());
+    }
+    auto emb = torch::empty({P, G, GT_HALF}, z.options());
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL(gt_pop_fwd_kernel, dim3((unsigned)G, (unsigned)P),
+                       dim3(GT_BLOCK), 0, stream, z.data_ptr<float>(),
+                       e.data_ptr<float>(), pl, pop.data_ptr<float>(),
+                       (long)n, (long)off,
+                       scratch.defined() ? scratch.data_ptr<float>() : nullptr,
+                       (long)slab, emb.data_ptr<float>());
+    return emb;
 }

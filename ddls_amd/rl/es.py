@@ -44,9 +44,21 @@ class ESConfig:
     eval_max_steps: int = 100000
     noise_seed: int = 0
     deterministic_eval: bool = False
+    # population evaluator only.  "torch": one GNN forward per member (the
+    # per-layer kernels).  "fused" (opt-in): all members in one launch of
+    # gt_pop_fwd_kernel (models.gnn.gnn_trunk_population); its embeddings
+    # differ from the per-layer kernels' in the last bits
+    population_trunk: str = "torch"
+
+    def __post_init__(self):
+        if self.population_trunk not in POPULATION_TRUNKS:
+            raise ValueError("ESConfig.population_trunk must be one of "
+                             f"{POPULATION_TRUNKS}, not "
+                             f"{self.population_trunk!r}")
 
 
 EVALUATORS = ("sequential", "population")
+POPULATION_TRUNKS = ("torch", "fused")
 
 
 def centered_ranks(x: np.ndarray) -> np.ndarray:
@@ -121,7 +133,8 @@ class ESTrainer:
                 self.env, self.policy, cfg.perturbation_pairs,
                 cfg.envs_per_member, eval_max_steps=cfg.eval_max_steps,
                 noise_seed=cfg.noise_seed,
-                deterministic=cfg.deterministic_eval)
+                deterministic=cfg.deterministic_eval,
+                trunk=cfg.population_trunk)
         return self._population
 
     def _get_flat(self) -> torch.Tensor:
@@ -184,6 +197,7 @@ class ESTrainer:
             "total_env_steps": self.total_env_steps,
             "update_time_s": time.perf_counter() - t0,
             "evaluator": 1,
+            "population_trunk": int(ev.fused_trunk),
             "eval_steps": res["eval_steps"],
             "truncated_envs": res["truncated_envs"],
             "tied_pairs": count_tied_pairs(fitness),

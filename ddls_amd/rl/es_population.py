@@ -8,7 +8,8 @@ uniforms — common random numbers, so a fitness difference is the effect of
 the perturbation alone.
 
 On a ``GpuEngine`` a generation is ``es_perturb`` (noise + population, one
-launch), ``P`` GNN forwards for the per-member embedding tables, one
+launch), ``P`` GNN forwards for the per-member embedding tables (or, with
+``trunk="fused"``, one ``gt_pop_fwd_kernel`` launch for all of them), one
 ``actor_population`` launch + one env step per step of the rollout, and
 ``es_update`` (``ops/hip/es_population.hip``).  On a ``CpuEngine`` the
 reference functions below do the same work in numpy / torch.  Each backend is
@@ -181,7 +182,8 @@ class PopulationEvaluator:
 
     def __init__(self, vec_env, policy, perturbation_pairs: int,
                  envs_per_member: int, eval_max_steps: int = 100000,
-                 noise_seed: int = 0, deterministic: bool = False):
+                 noise_seed: int = 0, deterministic: bool = False,
+                 trunk: str = "torch"):
         if not getattr(vec_env, "supports_population_eval", False):
             raise TypeError("PopulationEvaluator needs an env with "
                             "supports_population_eval (EngineVectorEnv)")
@@ -202,6 +204,15 @@ class PopulationEvaluator:
         self.mode = MODES["policy_greedy" if deterministic
                           else "policy_sample"]
         self.on_gpu = self.device.type == "cuda"
+        if trunk not in ("torch", "fused"):
+            raise ValueError("trunk must be 'torch' or 'fused', not "
+                             f"{trunk!r}")
+        if trunk == "fused" and not getattr(policy.gnn, "_trunk_ok", False):
+            raise ValueError("trunk='fused' is built for the tuned GNN shape "
+                             "only (policy.gnn._trunk_ok)")
+        self.trunk = trunk
+        # the population kernel runs (off the GPU "fused" is the plain chain)
+        self.fused_trunk = trunk == "fused" and self.on_gpu
         if self.on_gpu and not getattr(policy, "_fused_head_ok", False):
             raise ValueError("actor_population is built for the default head "
                              "shapes only (policy._fused_head_ok)")
@@ -291,9 +302,13 @@ class PopulationEvaluator:
 
     @torch.no_grad()
     def embeddings(self, pop: torch.Tensor) -> torch.Tensor:
-        """``model_emb_pop`` [P, M, 16]: one GNN forward per member."""
-        from ..models.gnn import graph_mean
+        """``model_emb_pop`` [P, M, 16]: one GNN forward per member, or with
+        ``trunk="fused"`` one ``gnn_trunk_population`` call on ``pop`` (the
+        GNN is the policy's first module: offset 0)."""
+        from ..models.gnn import gnn_trunk_population, graph_mean
         mb = self.env._models_batch
+        if self.trunk == "fused":
+            return gnn_trunk_population(pop, mb, 0).float()
         out = []
         for m in range(self.P):
             load_flat(self.scratch, pop[m])

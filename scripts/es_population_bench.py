@@ -16,6 +16,7 @@ The timer is a host clock around a generation that ends in
 
 Usage: python scripts/es_population_bench.py [--pairs 16]
            [--envs-per-member 8] [--eval-max-steps 64] [--generations 3]
+           [--trunk {torch,fused}]
 """
 import argparse
 import json
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--fragment-steps", type=int, default=16)
     ap.add_argument("--generations", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--trunk", choices=("torch", "fused"), default="torch",
+                    help="ESConfig.population_trunk of the population "
+                         "trainer")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -77,7 +81,8 @@ def main():
         return ESTrainer(venv, policy, ESConfig(
             perturbation_pairs=K, fragment_steps=args.fragment_steps,
             evaluator=evaluator, envs_per_member=E,
-            eval_max_steps=args.eval_max_steps), device=dev)
+            eval_max_steps=args.eval_max_steps,
+            population_trunk=args.trunk), device=dev)
 
     trainers = {"sequential": trainer("sequential"),
                 "population": trainer("population")}
@@ -104,7 +109,7 @@ def main():
     out = {"pairs": K, "envs_per_member": E, "B": B,
            "eval_max_steps": args.eval_max_steps,
            "fragment_steps": args.fragment_steps,
-           "generations": args.generations}
+           "generations": args.generations, "trunk": args.trunk}
     for name in trainers:
         t, n = float(np.median(times[name])), float(np.median(steps[name]))
         out[name] = {"ms_per_generation": t * 1e3,
