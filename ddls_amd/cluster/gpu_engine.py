@@ -18,6 +18,14 @@ from .vec_engine import (EngineSpec, EpisodeSchedule, PENDING, ST_MISS, ST_OK,
                          ST_STEP, build_episode_stats, compute_obs)
 
 
+# env_rollout.hip: why an env left its step loop, the most steps one launch
+# takes, and the order of the row tensors its binding takes
+WHY_T, WHY_DONE, WHY_MISS, WHY_ERR = 0, 1, 2, 3
+ROLLOUT_MAX_STEPS = 4096
+ROLLOUT_ROWS = ("gfull", "lp_all", "logp", "value", "u", "actions", "model",
+                "rewards", "dones", "ret", "nlive")
+
+
 def _pack_spec_tensors(spec: EngineSpec, device) -> Dict[str, torch.Tensor]:
     M = len(spec.models)
     D = len(spec.mds)
@@ -346,6 +354,81 @@ class GpuEngine:
                 self.hash_insert(mid, deg, vals)
                 T["status"][int(b)] = ST_STEP
         return T["status"]
+
+    def rollout_steps(self, actor_args: Dict, rows: Dict[str, torch.Tensor],
+                      T: int, t0=None, step0: int = 0,
+                      stop_at_done: bool = False, max_miss_rounds: int = 64):
+        """Steps ``t0[b] .. T-1`` of every env in ONE ``env_rollout_batch``
+        launch (``ops/hip/env_rollout.hip``): actor row, env step and the
+        stores of row ``t`` of ``rows`` (``[T, B, ...]`` tensors under the
+        names of ``ROLLOUT_ROWS``; ``ret`` / ``nlive`` are ``[B]``
+        accumulators).  ``actor_args`` holds ``mode``, ``sip_ml_cap``,
+        ``seed`` and, for the policy modes, ``model_emb`` and ``head``; the
+        Philox counter of row ``t`` is ``(b, step0 + t, 0)``.
+
+        An env stops early at an episode end or a memo miss.  Misses are
+        serviced here (insert + relaunch from the missed step) after ONE D2H
+        of the stop arrays per launch.  Returns ``(t0_next, done)``:
+        ``done`` lists ``(b, stop_t)`` for the envs whose episode ended, and
+        ``t0_next[b]`` is ``T`` for an env with nothing left — with
+        ``stop_at_done`` also for the done ones, otherwise their ``stop_t``,
+        the step to go on from once the caller has reset them."""
+        B = self.B
+        if not 1 <= T <= ROLLOUT_MAX_STEPS:
+            raise ValueError(f"rollout_steps: T must be in [1, "
+                             f"{ROLLOUT_MAX_STEPS}] per call, not {T}")
+        unknown = set(rows) - set(ROLLOUT_ROWS)
+        if unknown:
+            raise ValueError(f"rollout_steps: unknown rows {sorted(unknown)}")
+        dev = self.device
+        empty = torch.empty(0, device=dev)
+        row_list = [rows.get(k, empty) for k in ROLLOUT_ROWS]
+        t0 = np.zeros(B, dtype=np.int32) if t0 is None else \
+            np.array(t0, dtype=np.int32)
+        if t0.shape != (B,):
+            raise ValueError("rollout_steps: t0 must have one entry per env")
+        stop = torch.zeros((4, B), dtype=torch.int32, device=dev)
+        T_list = [self.T[k] for k in self._ORDER]
+        fscal, iscal = self._scalars()
+        done: List[tuple] = []
+        for _ in range(max_miss_rounds):
+            self.ext.env_rollout_batch(
+                T_list, fscal, iscal, actor_args.get("model_emb", empty),
+                actor_args.get("head", []), int(actor_args["mode"]),
+                int(actor_args.get("sip_ml_cap", -1)),
+                int(actor_args.get("seed", 0)) & (2 ** 64 - 1),
+                int(step0) & (2 ** 64 - 1), int(T),
+                torch.as_tensor(t0, device=dev), stop, row_list)
+            stop_t, why, miss_model, miss_action = stop.cpu().numpy()
+            if (why == WHY_ERR).any():
+                bad = np.flatnonzero(why == WHY_ERR).tolist()
+                raise RuntimeError(f"rollout_steps: env step error (ST_ERR) "
+                                   f"in envs {bad} at steps "
+                                   f"{stop_t[bad].tolist()}")
+            for b in np.flatnonzero(why == WHY_DONE):
+                done.append((int(b), int(stop_t[b])))
+            miss = np.flatnonzero(why == WHY_MISS)
+            # every env but the missed ones is finished with this call
+            t0 = np.where(why == WHY_MISS, stop_t, T).astype(np.int32)
+            if len(miss) == 0:
+                break
+            for b in miss:
+                mid = int(miss_model[b])
+                deg = int(self.spec.models[mid].action_to_degree[
+                    int(miss_action[b])])
+                vals = self.spec.memo.get((mid, deg))
+                if vals is None:
+                    raise RuntimeError(
+                        f"memo miss for (model {mid}, degree {deg}) with no "
+                        "compiled lookahead — spec.memo incomplete")
+                self.hash_insert(mid, deg, vals)
+        else:
+            raise RuntimeError("rollout_steps: memo misses left after "
+                               f"{max_miss_rounds} launches")
+        if not stop_at_done:
+            for b, st in done:
+                t0[b] = st
+        return t0, done
 
     # ------------------------------------------------------------------
     def episode_stats(self, b: int) -> Dict:

@@ -35,10 +35,13 @@ _SOURCES = [os.path.join(_HERE, "hip", "meanpool.hip"),
             os.path.join(_HERE, "hip", "batch_stage.hip"),
             os.path.join(_HERE, "hip", "actor.hip"),
             os.path.join(_HERE, "hip", "es_population.hip"),
+            os.path.join(_HERE, "hip", "env_rollout.hip"),
             os.path.join(_HERE, "hip", "bindings.hip")]
 # headers the sources include: not compiled on their own, but a built library
 # older than one of them is stale
-_HEADERS = [os.path.join(_HERE, "hip", "cs_stage.h")]
+_HEADERS = [os.path.join(_HERE, "hip", "cs_stage.h"),
+            os.path.join(_HERE, "hip", "actor_row.h"),
+            os.path.join(_HERE, "hip", "env_step_body.h")]
 
 
 def build_extensions(verbose: bool = False):

@@ -22,98 +22,10 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <vector>
 
-#define WAVE 64
+#include "actor_row.h"
+
 #define WPB 4
 #define BLOCK (WAVE * WPB)
-#define LN_EPS 1e-5f
-#define EMB 24
-#define H1 256
-#define GEMB 8
-#define NGF 17
-#define MASK_MIN (-3.4028234663852886e+38f)
-
-enum ActorMode {
-    POLICY_GREEDY = 0, POLICY_SAMPLE = 1, RANDOM = 2, NO_PARALLELISM = 3,
-    MIN_PARALLELISM = 4, MAX_PARALLELISM = 5, SIP_ML = 6, ACCEPTABLE_JCT = 7
-};
-
-__device__ __forceinline__ float awave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, WAVE);
-    return __shfl(v, 0, WAVE);
-}
-
-__device__ __forceinline__ float awave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = fmaxf(v, __shfl_xor(v, off, WAVE));
-    return v;
-}
-
-// first output word of Philox4x32-10
-__device__ __forceinline__ unsigned philox_word0(unsigned c0, unsigned c1,
-                                                 unsigned c2, unsigned c3,
-                                                 unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0);
-        const unsigned lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2);
-        const unsigned lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
-
-__device__ __forceinline__ int lowest_bit(unsigned v) { return __ffs(v) - 1; }
-__device__ __forceinline__ int highest_bit(unsigned v) { return 31 - __clz(v); }
-
-// the baselines of envs/actors.py on the bit set of valid actions (wave
-// uniform: every lane computes the same answer)
-__device__ __forceinline__ int heuristic_action(
-        int mode, unsigned vb, int A, float u, int sip_ml_cap,
-        double seq, double acc) {
-    const int n = __popc(vb);
-    // len(valid) <= 1: the count-based actors answer 0, the others valid[0]
-    if (n == 0 || mode == NO_PARALLELISM || mode == MIN_PARALLELISM) {
-        if (n <= 1) return 0;
-    }
-    if (n == 1) return lowest_bit(vb);
-    const int last = highest_bit(vb);
-    switch (mode) {
-    case NO_PARALLELISM:
-        return 1;
-    case MIN_PARALLELISM:
-        return (n > 2) ? 2 : 1;
-    case MAX_PARALLELISM:
-        return last;
-    case SIP_ML:
-        return (sip_ml_cap >= 0) ? min(sip_ml_cap, last) : last;
-    case ACCEPTABLE_JCT: {
-        const double want = ceil(seq / acc);
-        if (!(want <= (double)A)) return last;   // also NaN / +inf
-        const int w = (want > 0.0) ? (int)want : 0;
-        const unsigned ge = (w >= 32) ? 0u : (vb & ~((1u << w) - 1u));
-        return ge ? lowest_bit(ge) : last;
-    }
-    case RANDOM: {
-        // valid[1:][min(n-2, floor(u*(n-1)))]
-        int idx = (int)floorf(u * (float)(n - 1));
-        idx = min(idx, n - 2);
-        unsigned rest = vb & (vb - 1u);          // drop valid[0]
-        for (int i = 0; i < idx; ++i) rest &= rest - 1u;
-        return lowest_bit(rest);
-    }
-    default:
-        return 0;
-    }
-}
 
 template <bool POLICY>
 __global__ void __launch_bounds__(BLOCK)
@@ -159,129 +71,28 @@ actor_kernel(const float* __restrict__ obs_gf,      // [B,17]
 
     const int wave = threadIdx.x / WAVE;
     const int lane = threadIdx.x % WAVE;
+    const ActorHead W = {ln_w, ln_b, bg, b1p, W2p, b2p, b1v, W2v, b2v, H1};
     for (int r = blockIdx.x * WPB + wave; r < B; r += gridDim.x * WPB) {
         const int mid = obs_model[r];
         if (done[r] != 0 || mid < 0 || mid >= M) {   // wave uniform
             if (lane == 0) actions[r] = 0;
             continue;
         }
-        const float mk = (lane < A) ? obs_mask[(long)r * A + lane] : 0.0f;
-        const unsigned vb = (unsigned)__ballot(lane < A && mk > 0.0f);
-        const unsigned x = philox_word0((unsigned)r, step_lo, step_hi, 0u,
-                                        seed_lo, seed_hi);
-        const float u = (float)(x >> 8) * 5.9604644775390625e-08f;  // 2^-24
-
-        if constexpr (!POLICY) {
-            double seq = 0.0, acc = 0.0;
-            if (mode == ACCEPTABLE_JCT) {
-                const int k = obs_sched[r];
-                seq = model_seq[mid];
-                // an out-of-range schedule slot reads as "never reached"
-                acc = (k >= 0 && k < SCH) ? sch_acc[(long)r * SCH + k] : 0.0;
-            }
-            const int a = heuristic_action(mode, vb, A, u, sip_ml_cap, seq,
-                                           acc);
-            if (lane == 0) {
-                actions[r] = a;
-                if (mode == RANDOM && u_out != nullptr) u_out[r] = u;
-            }
-            continue;
-        }
-        if constexpr (POLICY) {
-        // ---- policy head: LN(gf ++ mask) -> graph Linear -> concat ----
-        float v = 0.0f;
-        if (lane < NGF) v = obs_gf[(long)r * NGF + lane];
-        else if (lane < Fg) v = obs_mask[(long)r * A + (lane - NGF)];
-        if (lane < Fg) gfull[(long)r * Fg + lane] = v;
-        const float mean = awave_sum(v) / Fg;
-        const float d = (lane < Fg) ? v - mean : 0.0f;
-        const float var = awave_sum(d * d) / Fg;
-        const float inv_sigma = rsqrtf(var + LN_EPS);
-        if (lane < Fg)
-            ylns[wave][lane] = d * inv_sigma * ln_w[lane] + ln_b[lane];
-        __builtin_amdgcn_wave_barrier();
-        if (lane < GEMB) {
-            float ge = bg[lane];
-            for (int k = 0; k < Fg; ++k)
-                ge = fmaf(wgs[lane][k], ylns[wave][k], ge);
-            embs[wave][16 + lane] = ge;
-        }
-        if (lane < 16) embs[wave][lane] = model_emb[(long)mid * 16 + lane];
-        __builtin_amdgcn_wave_barrier();
-
-        // policy branch
-#pragma unroll
-        for (int i = 0; i < H1 / WAVE; ++i) {
-            const int j = lane + WAVE * i;
-            float a1 = b1p[j];
-#pragma unroll
-            for (int k = 0; k < EMB; ++k)
-                a1 = fmaf(w1s[0][j][k], embs[wave][k], a1);
-            h1s[wave][j] = fmaxf(a1, 0.0f);
-        }
-        __builtin_amdgcn_wave_barrier();
-        float lg = -INFINITY;
-        if (lane < A) {
-            lg = b2p[lane];
-            const float* w2row = W2p + (long)lane * H1;
-            for (int j = 0; j < H1; ++j)
-                lg = fmaf(w2row[j], h1s[wave][j], lg);
-            // torch: logits + clamp(log(mask), min=float32_min)
-            lg += (mk > 0.0f) ? logf(mk) : MASK_MIN;
-        }
-        __builtin_amdgcn_wave_barrier();
-        // value branch
-#pragma unroll
-        for (int i = 0; i < H1 / WAVE; ++i) {
-            const int j = lane + WAVE * i;
-            float a1 = b1v[j];
-#pragma unroll
-            for (int k = 0; k < EMB; ++k)
-                a1 = fmaf(w1s[1][j][k], embs[wave][k], a1);
-            h1s[wave][j] = fmaxf(a1, 0.0f);
-        }
-        __builtin_amdgcn_wave_barrier();
-        float vp = 0.0f;
-#pragma unroll
-        for (int i = 0; i < H1 / WAVE; ++i) {
-            const int j = lane + WAVE * i;
-            vp = fmaf(W2v[j], h1s[wave][j], vp);
-        }
-        vp = awave_sum(vp) + b2v[0];
-
-        // max-subtracted log-softmax over the A lanes
-        const float mx = awave_max(lg);
-        const float ex = (lane < A) ? expf(lg - mx) : 0.0f;
-        const float lse = logf(awave_sum(ex));
-        const float lp = (lane < A) ? lg - mx - lse : -INFINITY;
-        if (lane < A) lp_all[(long)r * A + lane] = lp;
-
-        int act;
-        if (mode == POLICY_GREEDY) {
-            // argmax of the masked logits, ties to the lowest index
-            const unsigned long long top = __ballot(lane < A && lg == mx);
-            act = __ffsll((long long)top) - 1;
-            if (act < 0) act = 0;                // all-NaN logits
-        } else {
-            // inverse CDF: first valid a with u < cum, else the last valid
-            const float p = (lane < A) ? expf(lp) : 0.0f;
-            float cum = 0.0f;
-            act = -1;
-            for (int a = 0; a < A; ++a) {
-                cum += __shfl(p, a, WAVE);
-                if (act < 0 && ((vb >> a) & 1u) && u < cum) act = a;
-            }
-            if (act < 0) act = vb ? highest_bit(vb) : 0;
-        }
-        const float lpa = __shfl(lp, act, WAVE);
-        if (lane == 0) {
-            actions[r] = act;
-            logp[r] = lpa;
-            value[r] = vp;
-            if (u_out != nullptr) u_out[r] = u;
-        }
-        __builtin_amdgcn_wave_barrier();
-        }  // POLICY
+        double seq = 0.0;
+        if (!POLICY && mode == ACCEPTABLE_JCT) seq = model_seq[mid];
+        const ActorRowOut out = {
+            POLICY ? gfull + (long)r * Fg : nullptr,
+            POLICY ? lp_all + (long)r * A : nullptr,
+            POLICY ? logp + r : nullptr, POLICY ? value + r : nullptr,
+            u_out != nullptr ? u_out + r : nullptr};
+        const int act = actor_row<POLICY>(
+            lane, (unsigned)r, obs_gf + (long)r * NGF, obs_mask + (long)r * A,
+            POLICY ? model_emb + (long)mid * 16 : nullptr, obs_sched[r], seq,
+            sch_acc + (long)r * SCH, SCH,
+            (const float (*)[H1][EMB + 1])w1s, wgs, ylns[wave], embs[wave],
+            h1s[wave], W, out, A, mode, sip_ml_cap, seed_lo, seed_hi,
+            step_lo, step_hi);
+        if (lane == 0) actions[r] = act;
     }
 }
 

@@ -183,6 +183,12 @@ void actor_population(torch::Tensor obs_gf, torch::Tensor obs_mask,
                       uint64_t seed, uint64_t step, torch::Tensor actions,
                       torch::Tensor lp_all, torch::Tensor logp,
                       torch::Tensor value, torch::Tensor u);
+std::vector<int64_t> env_rollout_batch(
+    std::vector<torch::Tensor> T, std::vector<double> fscal,
+    std::vector<int64_t> iscal, torch::Tensor model_emb,
+    std::vector<torch::Tensor> head, int64_t mode, int64_t sip_ml_cap,
+    uint64_t seed, uint64_t step0, int64_t steps, torch::Tensor t0,
+    torch::Tensor stop, std::vector<torch::Tensor> rows);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("row_mlp", &row_mlp, "fused LN+Linear+ReLU over rows");
@@ -296,4 +302,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("actor_population", &actor_population,
           "actor_batch's policy modes with the head weights and embedding "
           "table of row b taken from population member b / E, one launch");
+    m.def("env_rollout_batch", &env_rollout_batch,
+          "fused rollout: actor row + env step for up to `steps` steps of "
+          "every env in one launch; stops an env at an episode end or a memo "
+          "miss and reports where in `stop` [4,B]");
 }

@@ -346,6 +346,44 @@ class DeviceActor:
             actions=actions, rows=rows)
         return out["actions"]
 
+    @torch.no_grad()
+    def rollout(self, eng, step0: int, T: int,
+                rows: Dict[str, torch.Tensor], t0=None,
+                stop_at_done: bool = False):
+        """``T`` steps of act + env step in one launch per stretch between
+        episode ends and memo misses (``GpuEngine.rollout_steps``); row ``t``
+        of ``rows`` (``[T, B, ...]``) is what ``act(eng, step0 + t)`` and the
+        step after it write.  Needs a ``GpuEngine`` this actor's kernel
+        serves; returns ``rollout_steps``' ``(t0_next, done)``."""
+        if self.is_policy and self.model_emb is None:
+            raise RuntimeError("DeviceActor.prepare(vec_env) must run before "
+                               "a policy actor acts")
+        if not (hasattr(eng, "rollout_steps") and self._kernel_serves(eng)):
+            raise RuntimeError("DeviceActor.rollout needs a GpuEngine and a "
+                               "head the actor kernel serves")
+        args = {"mode": self.mode, "seed": self.seed,
+                "sip_ml_cap": -1 if self.sip_ml_cap is None or self.is_policy
+                else int(self.sip_ml_cap)}
+        if self.is_policy:
+            if self._head is None:
+                self._head = head_params(self.policy_net)
+            if any(k not in rows for k in ROW_KEYS[:4]):
+                # a caller that wants actions only (evaluation): the head's
+                # rows still need somewhere to go
+                mask = eng.T["obs_mask"]
+                B, A = mask.shape
+                key = (mask.device, T, B, A)
+                if key not in self._scratch:
+                    z = lambda *s: torch.zeros(s, device=mask.device)
+                    self._scratch[key] = {
+                        "gfull": z(T, B, 17 + A), "lp_all": z(T, B, A),
+                        "logp": z(T, B), "value": z(T, B)}
+                rows = {**self._scratch[key], **rows}
+            args["model_emb"] = self.model_emb
+            args["head"] = self._head
+        return eng.rollout_steps(args, rows, T, t0=t0, step0=step0,
+                                 stop_at_done=stop_at_done)
+
     def _act_kernel(self, eng, step, rows, actions):
         from .. import ops as hip_ops
         ext = hip_ops.get_extension(required=True)

@@ -60,7 +60,7 @@ import torch.nn.functional as F
 from ..parallel import all_reduce_gradients
 from .device_replay import DeviceReplay, SumTreeReference
 from .impala import LEARNERS, ImpalaTrainer
-from .rollout import CompactObs
+from .rollout import CompactObs, check_rollout_sampler
 
 
 HEAD_STEPS = ("torch", "fused")
@@ -102,8 +102,11 @@ class DQNConfig:
     # per-layer kernels under autograd.  "fused": the kernels of
     # ops/hip/gnn_trunk.hip (policy.gnn._trunk_ok shapes only)
     trunk_step: str = "torch"
+    # see ImpalaConfig.rollout_sampler
+    rollout_sampler: str = "torch"
 
     def __post_init__(self):
+        check_rollout_sampler(self.rollout_sampler, "DQNConfig")
         if self.trunk_step not in TRUNK_STEPS:
             raise ValueError("DQNConfig.trunk_step must be 'torch' or "
                              f"'fused', not {self.trunk_step!r}")

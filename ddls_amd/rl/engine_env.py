@@ -85,6 +85,9 @@ class EngineVectorEnv:
     supports_device_resident = True
     # rollout() takes sampler="device" (one actor_batch launch per step)
     supports_device_sampler = True
+    # rollout() takes sampler="fused" (actor + env step of many steps in one
+    # env_rollout_batch launch)
+    supports_fused_sampler = True
     # rl.es_population.PopulationEvaluator may borrow spec / gen / models
     # batch / device / base_seed for an engine of its own
     supports_population_eval = True
@@ -198,10 +201,16 @@ class EngineVectorEnv:
         with one DeviceActor call in POLICY_SAMPLE mode (on a GpuEngine one
         ``actor_batch`` launch) that writes row ``t`` of the buffers directly;
         its Philox key is ``base_seed`` and its step counter lives on the
-        env.  The returned dict has the same keys, shapes and dtypes."""
-        if sampler not in ("torch", "device"):
-            raise ValueError("rollout sampler must be 'torch' or 'device', "
-                             f"not {sampler!r}")
+        env.  The returned dict has the same keys, shapes and dtypes.
+
+        ``sampler="fused"`` computes the same numbers as ``"device"`` with
+        one ``env_rollout_batch`` launch per stretch between episode ends and
+        memo misses instead of two launches and two host syncs per step (on a
+        GpuEngine whose head the actor kernel serves; elsewhere it is the
+        ``"device"`` path)."""
+        if sampler not in ("torch", "device", "fused"):
+            raise ValueError("rollout sampler must be 'torch', 'device' or "
+                             f"'fused', not {sampler!r}")
         dev = self.device
         B = self.num_envs
         A = self.spec.A
@@ -221,14 +230,25 @@ class EngineVectorEnv:
         buf_dones = torch.empty((T, B), dtype=torch.bool, device=dev)
 
         actor = None
-        if sampler == "device":
+        if sampler in ("device", "fused"):
             from .device_actor import DeviceActor
             actor = DeviceActor.policy(policy, deterministic=False,
                                        seed=self.base_seed)
             actor.prepare(self, model_emb=model_emb)
             buf_u = torch.empty((T, B), device=dev)
 
-        for t in range(T):
+        fused = (sampler == "fused" and hasattr(eng, "rollout_steps")
+                 and actor._kernel_serves(eng))
+        if fused:
+            buf_dones = torch.empty((T, B), dtype=torch.uint8, device=dev)
+            self._rollout_fused(actor, T, {
+                "gfull": buf_gfull, "lp_all": buf_lp_all, "logp": buf_logp,
+                "value": buf_values, "u": buf_u, "actions": buf_actions,
+                "model": buf_model, "rewards": buf_rewards,
+                "dones": buf_dones})
+            buf_dones = buf_dones != 0
+
+        for t in range(0 if fused else T):
             if actor is not None:
                 buf_model[t] = eng.T["obs_model"]
                 actions = actor.act(eng, self._sampler_step, rows={
@@ -259,14 +279,8 @@ class EngineVectorEnv:
             buf_dones[t] = done
             if bool(done.any()):
                 for b in torch.nonzero(done).flatten().tolist():
-                    es = eng.episode_stats(b)
-                    self.completed_episode_stats.append(es)
-                    self._jct_base_count += es["num_jobs_completed"]
-                    self._jct_base_sum += float(
-                        np.sum(es["job_completion_time"]))
-                    self.episode_counters[b] += 1
-                    self.scheds[b] = self._drain(b)
-                    eng.reset_env(b, self.scheds[b])
+                    self._record_episode(eng.episode_stats(b))
+                    self._next_episode(b)
 
         # bootstrap values of the final obs
         gf = eng.T["obs_gf"]
@@ -316,6 +330,38 @@ class EngineVectorEnv:
             "dones": buf_dones.cpu().numpy(),
             "bootstrap_values": bootstrap.cpu().numpy(),
         }
+
+    def _record_episode(self, es: dict):
+        self.completed_episode_stats.append(es)
+        self._jct_base_count += es["num_jobs_completed"]
+        self._jct_base_sum += float(np.sum(es["job_completion_time"]))
+
+    def _next_episode(self, b: int):
+        self.episode_counters[b] += 1
+        self.scheds[b] = self._drain(b)
+        self.eng.reset_env(b, self.scheds[b])
+
+    def _rollout_fused(self, actor, T: int, bufs: Dict[str, torch.Tensor]):
+        """Fill rows ``0 .. T-1`` of ``bufs`` (``[T, B, ...]``) with
+        ``DeviceActor.rollout``: launch, give every env whose episode ended
+        its next schedule, go on from that env's stop step.  Episode stats
+        are recorded in (stop step, env) order, the per-step loop's order."""
+        from ..cluster.gpu_engine import ROLLOUT_MAX_STEPS
+        eng = self.eng
+        ended = []
+        for c0 in range(0, T, ROLLOUT_MAX_STEPS):
+            n = min(T - c0, ROLLOUT_MAX_STEPS)
+            rows = {k: v[c0:c0 + n] for k, v in bufs.items()}
+            t0 = None
+            while t0 is None or (t0 < n).any():
+                t0, done = actor.rollout(eng, self._sampler_step + c0, n,
+                                         rows, t0=t0)
+                for b, stop_t in done:
+                    ended.append((c0 + stop_t, b, eng.episode_stats(b)))
+                    self._next_episode(b)
+        for _, _, es in sorted(ended, key=lambda e: e[:2]):
+            self._record_episode(es)
+        self._sampler_step += T
 
     # ------------------------------------------------------------------
     def drain_episode_stats(self) -> List[dict]:

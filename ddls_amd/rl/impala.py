@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from ..parallel import all_reduce_gradients
-from .rollout import CompactObs, collate
+from .rollout import CompactObs, check_rollout_sampler, collate
 
 
 @dataclass
@@ -55,6 +55,13 @@ class ImpalaConfig:
     # batch + fused V-trace loss kernels (needs an env with
     # supports_device_resident, else falls back to "torch" with a warning)
     learner: str = "torch"
+    # how the engine env samples actions during rollouts (see
+    # rl/rollout.py ROLLOUT_SAMPLERS); forwarded only when it is not "torch"
+    # and the env advertises supports_device_sampler
+    rollout_sampler: str = "torch"
+
+    def __post_init__(self):
+        check_rollout_sampler(self.rollout_sampler, "ImpalaConfig")
 
 
 LEARNERS = ("torch", "device")
@@ -203,11 +210,17 @@ class ImpalaTrainer:
         steps = num_steps if num_steps is not None else max(
             1, self.config.train_batch_size // n_envs)
         if hasattr(self.env, "rollout"):
+            kw = {}
+            # getattr: subclasses may hold configs without the switch
+            sampler = getattr(self.config, "rollout_sampler", "torch")
+            if sampler != "torch" and getattr(
+                    self.env, "supports_device_sampler", False):
+                kw["sampler"] = sampler
             if self._device_learner():
                 data = self.env.rollout(self.policy, steps,
-                                        device_resident=True)
+                                        device_resident=True, **kw)
             else:
-                data = self.env.rollout(self.policy, steps)
+                data = self.env.rollout(self.policy, steps, **kw)
             self.total_env_steps += steps * n_envs
             return data
         obs_buf, act_buf, logp_buf, val_buf, rew_buf, done_buf = \

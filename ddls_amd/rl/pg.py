@@ -13,6 +13,7 @@ import torch
 
 from ..parallel import all_reduce_gradients
 from .impala import ImpalaTrainer
+from .rollout import check_rollout_sampler
 
 
 @dataclass
@@ -22,6 +23,11 @@ class PGConfig:
     gamma: float = 0.99
     train_batch_size: int = 200
     grad_clip: Optional[float] = None
+    # see ImpalaConfig.rollout_sampler
+    rollout_sampler: str = "torch"
+
+    def __post_init__(self):
+        check_rollout_sampler(self.rollout_sampler, "PGConfig")
 
 
 class PGTrainer(ImpalaTrainer):

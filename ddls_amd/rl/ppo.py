@@ -20,7 +20,8 @@ import torch.nn.functional as F
 
 from ..models.gnn import GNNPolicy
 from ..parallel import all_reduce_gradients, get_rank
-from .rollout import CompactObs, VectorEnv, collate
+from .rollout import (CompactObs, VectorEnv, check_rollout_sampler,
+                      collate)
 
 
 @dataclass
@@ -49,10 +50,15 @@ class PPOConfig:
     # path exactly.  DDLS_AMD_DISABLE_DEVICE_BATCH=1 forces "off".
     device_batch: str = "auto"
     # how the engine env samples actions during rollouts: "torch" (head +
-    # Categorical per step) or "device" (rl/device_actor.py: one actor_batch
-    # launch per step).  Forwarded only when it is not "torch" and the env
+    # Categorical per step), "device" (rl/device_actor.py: one actor_batch
+    # launch per step) or "fused" (same numbers as "device", actor + env step
+    # of the whole rollout in one env_rollout_batch launch per stretch between
+    # episode ends).  Forwarded only when it is not "torch" and the env
     # advertises supports_device_sampler.
     rollout_sampler: str = "torch"
+
+    def __post_init__(self):
+        check_rollout_sampler(self.rollout_sampler, "PPOConfig")
 
 
 class PPOTrainer:

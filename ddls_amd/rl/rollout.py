@@ -16,6 +16,17 @@ import torch
 
 from ..models.gnn import GraphBatch
 
+# how an env with a rollout() samples actions (rl/engine_env.py): "torch"
+# (head + Categorical per step), "device" (one actor_batch launch per step)
+# or "fused" (actor + env step of many steps in one env_rollout_batch launch)
+ROLLOUT_SAMPLERS = ("torch", "device", "fused")
+
+
+def check_rollout_sampler(name: str, owner: str) -> None:
+    if name not in ROLLOUT_SAMPLERS:
+        raise ValueError(f"{owner}.rollout_sampler must be one of "
+                         f"{ROLLOUT_SAMPLERS}, not {name!r}")
+
 
 @dataclass
 class CompactObs:

@@ -217,6 +217,7 @@ def build_trainer_from_config(cfg: dict, device=None):
             learner=str(algo.get("learner", "torch")),
             head_step=str(algo.get("head_step", "torch")),
             trunk_step=str(algo.get("trunk_step", "torch")),
+            rollout_sampler=str(algo.get("rollout_sampler", "torch")),
             prioritized_replay=bool(algo.get("prioritized_replay", False)),
             prioritized_replay_alpha=algo.get(
                 "prioritized_replay_alpha", 0.9),
@@ -228,7 +229,9 @@ def build_trainer_from_config(cfg: dict, device=None):
         pg_cfg = PGConfig(lr=algo.get("lr", 4e-4),
                           gamma=algo.get("gamma", 0.99),
                           train_batch_size=algo.get("train_batch_size", 200),
-                          grad_clip=algo.get("grad_clip"))
+                          grad_clip=algo.get("grad_clip"),
+                          rollout_sampler=str(algo.get("rollout_sampler",
+                                                       "torch")))
         return PGTrainer(venv, policy, pg_cfg, device=device)
     if algo.get("name", "ppo") == "impala":
         from ..rl.impala import ImpalaConfig, ImpalaTrainer
@@ -243,7 +246,8 @@ def build_trainer_from_config(cfg: dict, device=None):
             c_clip=algo.get("vtrace_clip_c_threshold", 1.0),
             train_batch_size=algo.get("train_batch_size", 4000),
             vtrace_drop_last_ts=algo.get("vtrace_drop_last_ts", True),
-            learner=str(algo.get("learner", "torch")))
+            learner=str(algo.get("learner", "torch")),
+            rollout_sampler=str(algo.get("rollout_sampler", "torch")))
         return ImpalaTrainer(venv, policy, imp_cfg, device=device)
     ppo_cfg = PPOConfig(
         lr=algo.get("lr", 2.785e-4),
@@ -259,6 +263,7 @@ def build_trainer_from_config(cfg: dict, device=None):
         train_batch_size=algo.get("train_batch_size", 4000),
         num_sgd_iter=algo.get("num_sgd_iter", 50),
         # YAML reads a bare on/off as a boolean
+        rollout_sampler=str(algo.get("rollout_sampler", "torch")),
         device_batch={True: "on", False: "off"}.get(
             algo.get("device_batch", "auto"),
             str(algo.get("device_batch", "auto"))))

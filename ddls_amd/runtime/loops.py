@@ -84,10 +84,16 @@ class EngineEvalLoop:
     plus ``seed``.  ``episode_return`` is the f64 sum of ``T["reward"]`` in
     step order over the steps the env was live for (a skipped env keeps a
     stale reward) — not the engine's own ``ep_return``.
+
+    ``fused_steps > 0`` (GpuEngine only) advances a wave ``fused_steps`` steps
+    per ``DeviceActor.rollout`` call — one launch per stretch between memo
+    misses instead of two launches and three host syncs per step; the return
+    and the step count come from the kernel's accumulators.  Same results.
     """
 
     def __init__(self, actor, env_fn, device, num_envs: Optional[int] = None,
-                 max_steps: int = 100000, spec=None, proto_env=None):
+                 max_steps: int = 100000, spec=None, proto_env=None,
+                 fused_steps: int = 0):
         import torch
         from ..cluster.vec_engine import compile_engine_spec
         from ..rl.engine_env import build_models_batch
@@ -95,6 +101,9 @@ class EngineEvalLoop:
         self.device = torch.device(device)
         self.num_envs = num_envs
         self.max_steps = max_steps
+        if fused_steps < 0:
+            raise ValueError("fused_steps must be >= 0")
+        self.fused_steps = int(fused_steps)
         if proto_env is None:
             proto_env = env_fn()
             proto_env.reset(seed=987654321)
@@ -133,7 +142,21 @@ class EngineEvalLoop:
         ret = torch.zeros(B, dtype=torch.float64, device=dev)
         nsteps = torch.zeros(B, dtype=torch.int64, device=dev)
         step = 0
-        while step < self.max_steps:
+        fused = self.fused_steps if hasattr(eng, "rollout_steps") else 0
+        if fused:
+            from ..cluster.gpu_engine import ROLLOUT_MAX_STEPS
+            nsteps_acc = {"ret": ret, "nlive": nsteps}
+            left = np.ones(B, dtype=bool)
+        while fused and step < self.max_steps and left.any():
+            # finished envs stay done: they are never relaunched
+            n = min(fused, self.max_steps - step, ROLLOUT_MAX_STEPS)
+            _, done = self.actor.rollout(
+                eng, step, n, nsteps_acc, t0=np.where(left, 0, n),
+                stop_at_done=True)
+            for b, _ in done:
+                left[b] = False
+            step += n
+        while not fused and step < self.max_steps:
             live = eng.T["done"] == 0
             if not bool(live.any()):
                 break

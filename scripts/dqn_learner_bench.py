@@ -75,6 +75,9 @@ def main():
                     default="torch", help="the device learner's Q-head step")
     ap.add_argument("--trunk-step", choices=("torch", "fused"),
                     default="torch", help="the device learner's GNN trunk")
+    ap.add_argument("--sampler", choices=("torch", "device", "fused"),
+                    default="torch",
+                    help="DQNConfig.rollout_sampler of every trainer")
     ap.add_argument("--count-launches", action="store_true")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
@@ -119,6 +122,7 @@ def main():
             sgd_minibatch_size=algo["sgd_minibatch_size"],
             num_sgd_iter=algo["num_sgd_iter"], learner=learner,
             head_step=head_step, trunk_step=trunk_step,
+            rollout_sampler=args.sampler,
             prioritized_replay=args.prioritized,
             prioritized_replay_alpha=algo["prioritized_replay_alpha"],
             prioritized_replay_beta=algo["prioritized_replay_beta"],
@@ -163,7 +167,7 @@ def main():
            "num_sgd_iter": algo["num_sgd_iter"], "n_step": algo["n_step"],
            "iters": args.iters, "warmup": args.warmup,
            "prioritized": args.prioritized, "head_step": args.head_step,
-           "trunk_step": args.trunk_step}
+           "trunk_step": args.trunk_step, "sampler": args.sampler}
     for name in trainers:
         assert last[name]["learner"] == (0 if name == "torch" else 1)
         assert last[name].get("head_step", 0) == int(

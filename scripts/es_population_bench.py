@@ -43,6 +43,10 @@ def main():
     ap.add_argument("--trunk", choices=("torch", "fused"), default="torch",
                     help="ESConfig.population_trunk of the population "
                          "trainer")
+    ap.add_argument("--sampler", choices=("device", "fused"),
+                    default="device",
+                    help="sampler of the single-policy rollout the step loop "
+                         "is compared against")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -151,10 +155,12 @@ def main():
     policy = trainers["sequential"].policy
     n_steps = max(res["eval_steps"], 1)
     with torch.no_grad():
-        venv.rollout(policy, n_steps, device_resident=True, sampler="device")
+        venv.rollout(policy, n_steps, device_resident=True,
+                     sampler=args.sampler)
         sync()
         t0 = time.perf_counter()
-        venv.rollout(policy, n_steps, device_resident=True, sampler="device")
+        venv.rollout(policy, n_steps, device_resident=True,
+                     sampler=args.sampler)
         sync()
         single_ms = (time.perf_counter() - t0) * 1e3
     out["step_loop_vs_single_policy"] = {

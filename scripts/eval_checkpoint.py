@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--seeds", type=int, default=None,
                     help="number of consecutive eval seeds (default: "
                          "--episodes)")
+    ap.add_argument("--fused-steps", type=int, default=0,
+                    help="engine backend on a GPU: steps per fused rollout "
+                         "launch (0: one actor and one env launch per step)")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args()
 
@@ -54,7 +57,7 @@ def main():
                                        seed=eval_seed)
         # raises the engine's ValueError for a config it does not support
         loop = EngineEvalLoop(dev_actor, lambda: build_env_from_config(cfg),
-                              device)
+                              device, fused_steps=args.fused_steps)
         rows = []
         for ep, r in enumerate(loop.run(range(eval_seed,
                                               eval_seed + episodes))):

@@ -30,6 +30,9 @@ def main():
     ap.add_argument("--seeds", type=int, default=1,
                     help="number of consecutive seeds, starting at the "
                          "config's seed")
+    ap.add_argument("--fused-steps", type=int, default=0,
+                    help="engine backend on a GPU: steps per fused rollout "
+                         "launch (0: one actor and one env launch per step)")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args()
 
@@ -64,7 +67,7 @@ def main():
         seed_everything(seed)
         # raises the engine's ValueError for a config it does not support
         loop = EngineEvalLoop(None, lambda: build_env_from_config(cfg),
-                              device)
+                              device, fused_steps=args.fused_steps)
         results = {}
         for actor_name in cfg.get("actors", list(ACTORS)):
             kwargs = {"seed": seed}
