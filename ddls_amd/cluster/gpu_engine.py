@@ -24,6 +24,8 @@ WHY_T, WHY_DONE, WHY_MISS, WHY_ERR = 0, 1, 2, 3
 ROLLOUT_MAX_STEPS = 4096
 ROLLOUT_ROWS = ("gfull", "lp_all", "logp", "value", "u", "actions", "model",
                 "rewards", "dones", "ret", "nlive")
+# envs per workgroup of the population rollout (docs/KERNELS.md says why)
+POP_ROLLOUT_WPB = 1
 
 
 def _pack_spec_tensors(spec: EngineSpec, device) -> Dict[str, torch.Tensor]:
@@ -429,6 +431,90 @@ class GpuEngine:
             for b, st in done:
                 t0[b] = st
         return t0, done
+
+    def rollout_population(self, pop: torch.Tensor,
+                           model_emb_pop: torch.Tensor, head_offs, E: int,
+                           mode: int, seed: int, step0: int, T: int,
+                           ret: torch.Tensor, nlive: torch.Tensor, t0=None,
+                           actions: Optional[torch.Tensor] = None,
+                           max_wpb: int = POP_ROLLOUT_WPB,
+                           max_miss_rounds: int = 64):
+        """``rollout_steps`` for an ES population, with ``stop_at_done``
+        semantics: ONE ``env_rollout_population`` launch plays steps
+        ``t0[b] .. T-1`` of every env, row ``b = m * E + e`` with the head
+        (``head_offs`` inside ``pop[m]``) and the embedding table
+        (``model_emb_pop[m]``) of member ``m``; the Philox counter of row
+        ``t`` is ``(e, step0 + t, 0)``.  ``ret`` (f64) and ``nlive`` (i64) are
+        ``[B]`` accumulators; ``actions`` is an optional i64 ``[T, B]`` row.
+
+        Memo misses are serviced as in ``rollout_steps`` (one D2H of the stop
+        array per launch).  Returns ``(reached, ended)``: the step each env
+        stopped at (``t0[b]`` for one that was done before the call) and
+        whether its episode is over.  An env that ended before the last step
+        any env played here is left as the step loop leaves it: ``status`` and
+        ``actions`` 0."""
+        B = self.B
+        if not 1 <= T <= ROLLOUT_MAX_STEPS:
+            raise ValueError(f"rollout_population: T must be in [1, "
+                             f"{ROLLOUT_MAX_STEPS}] per call, not {T}")
+        if mode not in (0, 1):
+            raise ValueError("rollout_population serves the policy modes "
+                             f"only, not mode {mode}")
+        if pop.dim() != 2 or B != pop.shape[0] * int(E):
+            raise ValueError(f"rollout_population: B = {B} is not P * E = "
+                             f"{tuple(pop.shape)[:1]} * {E}")
+        dev = self.device
+        t0 = np.zeros(B, dtype=np.int32) if t0 is None else \
+            np.array(t0, dtype=np.int32)
+        if t0.shape != (B,):
+            raise ValueError("rollout_population: t0 must have one entry per "
+                             "env")
+        if actions is None:
+            actions = torch.empty(0, dtype=torch.int64, device=dev)
+        stop = torch.zeros((4, B), dtype=torch.int32, device=dev)
+        T_list = [self.T[k] for k in self._ORDER]
+        fscal, iscal = self._scalars()
+        reached = t0.copy()
+        ended = np.zeros(B, dtype=bool)
+        for _ in range(max_miss_rounds):
+            self.ext.env_rollout_population(
+                T_list, fscal, iscal, pop, model_emb_pop,
+                [int(o) for o in head_offs], int(E), int(mode),
+                int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(T),
+                torch.as_tensor(t0, device=dev), stop, ret, nlive, actions,
+                int(max_wpb))
+            stop_t, why, miss_model, miss_action = stop.cpu().numpy()
+            if (why == WHY_ERR).any():
+                bad = np.flatnonzero(why == WHY_ERR).tolist()
+                raise RuntimeError(f"rollout_population: env step error "
+                                   f"(ST_ERR) in envs {bad} at steps "
+                                   f"{stop_t[bad].tolist()}")
+            ran = t0 < T
+            reached = np.where(ran, stop_t, reached)
+            ended |= ran & (why == WHY_DONE)
+            miss = np.flatnonzero(why == WHY_MISS)
+            t0 = np.where(why == WHY_MISS, stop_t, T).astype(np.int32)
+            if len(miss) == 0:
+                break
+            for b in miss:
+                mid = int(miss_model[b])
+                deg = int(self.spec.models[mid].action_to_degree[
+                    int(miss_action[b])])
+                vals = self.spec.memo.get((mid, deg))
+                if vals is None:
+                    raise RuntimeError(
+                        f"memo miss for (model {mid}, degree {deg}) with no "
+                        "compiled lookahead — spec.memo incomplete")
+                self.hash_insert(mid, deg, vals)
+        else:
+            raise RuntimeError("rollout_population: memo misses left after "
+                               f"{max_miss_rounds} launches")
+        stale = np.flatnonzero(ended & (reached < reached.max()))
+        if len(stale):
+            idx = torch.as_tensor(stale, device=dev)
+            self.T["status"].index_fill_(0, idx, 0)
+            self.T["actions"].index_fill_(0, idx, 0)
+        return reached, ended
 
     # ------------------------------------------------------------------
     def episode_stats(self, b: int) -> Dict:

@@ -1,7 +1,7 @@
 // One row of the device-side actors (actor.hip's contract: lane ownership,
 // fmaf chains and orders, Philox counter), as a __device__ function shared by
 // actor.hip (one launch per step) and env_rollout.hip (actor + env step, T
-// times in one launch).  Both callers run the SAME arithmetic, so their rows
+// times in one launch, for one policy or for a population of them).  Both callers run the SAME arithmetic, so their rows
 // are bit-equal.  The row reads its weights through plain pointers: actor.hip
 // passes LDS for the first-layer matrices and global memory for the rest,
 // env_rollout.hip passes LDS for all of them.
@@ -106,7 +106,8 @@ struct ActorHead {
     int w2p_ld;
 };
 
-// where a row's results go (policy modes: all but u required; u may be null)
+// where a row's results go; a null pointer leaves that result unwritten (the
+// population rollout keeps none of them)
 struct ActorRowOut {
     float *gfull, *lp_all, *logp, *value, *u;
 };
@@ -147,7 +148,7 @@ __device__ __forceinline__ int actor_row(
         float v = 0.0f;
         if (lane < NGF) v = gf[lane];
         else if (lane < Fg) v = mask[lane - NGF];
-        if (lane < Fg) out.gfull[lane] = v;
+        if (out.gfull != nullptr && lane < Fg) out.gfull[lane] = v;
         const float mean = awave_sum(v) / Fg;
         const float d = (lane < Fg) ? v - mean : 0.0f;
         const float var = awave_sum(d * d) / Fg;
@@ -209,7 +210,7 @@ __device__ __forceinline__ int actor_row(
         const float ex = (lane < A) ? expf(lg - mx) : 0.0f;
         const float lse = logf(awave_sum(ex));
         const float lp = (lane < A) ? lg - mx - lse : -INFINITY;
-        if (lane < A) out.lp_all[lane] = lp;
+        if (out.lp_all != nullptr && lane < A) out.lp_all[lane] = lp;
 
         int act;
         if (mode == POLICY_GREEDY) {
@@ -230,8 +231,8 @@ __device__ __forceinline__ int actor_row(
         }
         const float lpa = __shfl(lp, act, WAVE);
         if (lane == 0) {
-            out.logp[0] = lpa;
-            out.value[0] = vp;
+            if (out.logp != nullptr) out.logp[0] = lpa;
+            if (out.value != nullptr) out.value[0] = vp;
             if (out.u != nullptr) out.u[0] = u;
         }
         __builtin_amdgcn_wave_barrier();

@@ -189,6 +189,13 @@ std::vector<int64_t> env_rollout_batch(
     std::vector<torch::Tensor> head, int64_t mode, int64_t sip_ml_cap,
     uint64_t seed, uint64_t step0, int64_t steps, torch::Tensor t0,
     torch::Tensor stop, std::vector<torch::Tensor> rows);
+std::vector<int64_t> env_rollout_population(
+    std::vector<torch::Tensor> T, std::vector<double> fscal,
+    std::vector<int64_t> iscal, torch::Tensor pop,
+    torch::Tensor model_emb_pop, std::vector<int64_t> head_offs, int64_t E,
+    int64_t mode, uint64_t seed, uint64_t step0, int64_t steps,
+    torch::Tensor t0, torch::Tensor stop, torch::Tensor ret,
+    torch::Tensor nlive, torch::Tensor actions, int64_t max_wpb);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("row_mlp", &row_mlp, "fused LN+Linear+ReLU over rows");
@@ -306,4 +313,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused rollout: actor row + env step for up to `steps` steps of "
           "every env in one launch; stops an env at an episode end or a memo "
           "miss and reports where in `stop` [4,B]");
+    m.def("env_rollout_population", &env_rollout_population,
+          "fused rollout of an ES population: env_rollout_batch with the "
+          "head and embedding table of row b taken from member b / E of "
+          "`pop` and the Philox index b % E; keeps ret / nlive [B] only");
 }

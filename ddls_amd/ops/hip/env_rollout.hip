@@ -26,6 +26,17 @@
 // env_step_kernel run, with the Philox counter (b, step0 + t, 0): the result
 // is bit-equal to T alternations of those two kernels.
 //
+// Population variant (env_rollout_pop_kernel, for rl/es_population.py): the
+// grid is (ceil(E / WPB), P) and every wave of a workgroup serves member
+// m = blockIdx.y.  The workgroup stages member m's head from row m of the
+// [P, n] population matrix (pop + m * n + head_offs[i], 4-byte loads: rows
+// are not 16-byte aligned) and model_emb_pop[m]; wave `e` owns engine row
+// b = m * E + e and draws with the Philox index e, not b (common random
+// numbers: every member sees the uniforms of a batch of E rows).  Staging,
+// the LDS carve-up, the step loop and the stop protocol are the functions
+// below, shared by both kernels; the variant keeps no [T, B, ...] rows but
+// the optional actions row.
+//
 // Stop protocol (no inter-block waiting anywhere): a wave leaves its loop
 // when t == T (WHY_T), when the step set done (WHY_DONE, stop_t = t + 1),
 // when the step missed the memo (WHY_MISS, stop_t = t, state untouched, row t
@@ -33,6 +44,7 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <utility>
 #include <vector>
 
 #include "actor_row.h"
@@ -70,69 +82,77 @@ struct RolloutArgs {
   int T, emb_in_lds, wave_bytes;
 };
 
-template <bool POLICY>
-__global__ void __launch_bounds__(WAVE * MAX_WPB)
-env_rollout_kernel(EnvPtrs P, EnvDims D, RolloutArgs R) {
-  extern __shared__ __align__(16) char lds[];
-  const int A = D.A, B = D.B, Fg = NGF + A, M = R.M;
-  const int nthr = blockDim.x, wpb = blockDim.x / WAVE;
-  float* f = (float*)lds;
-  const float (*w1s)[H1][EMB + 1] = nullptr;
-  const float (*wgs)[64 + 1] = nullptr;
-  ActorHead W = {};
-  const float* embt = R.model_emb;
-  if constexpr (POLICY) {
-    float (*w1)[H1][EMB + 1] = (float (*)[H1][EMB + 1])f;
-    f += 2 * H1 * (EMB + 1);
-    float (*wg)[64 + 1] = (float (*)[64 + 1])f;
-    f += GEMB * (64 + 1);
-    float* w2p = f;  f += A * W2P_LD;
-    float* ln_w = f; f += 64;
-    float* ln_b = f; f += 64;
-    float* bg = f;   f += 8;
-    float* b1p = f;  f += H1;
-    float* b2p = f;  f += 32;
-    float* b1v = f;  f += H1;
-    float* w2v = f;  f += H1;
-    float* b2v = f;  f += 8;
-    for (int i = threadIdx.x; i < H1 * EMB; i += nthr) {
-      w1[0][i / EMB][i % EMB] = R.head[4][i];
-      w1[1][i / EMB][i % EMB] = R.head[8][i];
-    }
-    for (int i = threadIdx.x; i < GEMB * Fg; i += nthr)
-      wg[i / Fg][i % Fg] = R.head[2][i];
-    for (int i = threadIdx.x; i < A * H1; i += nthr)
-      w2p[(i / H1) * W2P_LD + i % H1] = R.head[6][i];
-    for (int i = threadIdx.x; i < H1; i += nthr) {
-      b1p[i] = R.head[5][i];
-      b1v[i] = R.head[9][i];
-      w2v[i] = R.head[10][i];
-    }
-    for (int i = threadIdx.x; i < Fg; i += nthr) {
-      ln_w[i] = R.head[0][i];
-      ln_b[i] = R.head[1][i];
-    }
-    if (threadIdx.x < GEMB) bg[threadIdx.x] = R.head[3][threadIdx.x];
-    if (threadIdx.x < A) b2p[threadIdx.x] = R.head[7][threadIdx.x];
-    if (threadIdx.x == 0) b2v[0] = R.head[11][0];
-    if (R.emb_in_lds) {
-      for (int i = threadIdx.x; i < M * 16; i += nthr) f[i] = R.model_emb[i];
-      embt = f;
-      f += M * 16;
-    }
-    // the waves' regions hold f64 scratch: keep them 8-byte aligned
-    f = (float*)lds + (((f - (float*)lds) + 1) & ~1L);
-    w1s = w1;
-    wgs = wg;
-    W = {ln_w, ln_b, bg, b1p, w2p, b2p, b1v, w2v, b2v, W2P_LD};
-    __syncthreads();
-  }
+// the staged head of a workgroup and where the waves' regions start
+struct HeadLds {
+  const float (*w1s)[H1][EMB + 1];
+  const float (*wgs)[64 + 1];
+  ActorHead W;
+  const float* embt;        // [M,16]: LDS when it fits, else global
+  float* waves;
+};
 
-  const int wave = threadIdx.x / WAVE;
-  const int lane = threadIdx.x % WAVE;
-  const int b = blockIdx.x * wpb + wave;
-  if (b >= B) return;                       // no block barrier below
-  char* mine = (char*)f + (long)wave * R.wave_bytes;
+// Stages the 12 head tensors (head_fwd's order; 4-byte loads, no alignment
+// assumed) and, with `emb_in_lds`, the embedding table into LDS.  The whole
+// workgroup calls this; it ends in the kernel's ONE block barrier.
+__device__ __forceinline__ HeadLds stage_head(
+    float* f, const float* const* head, const float* model_emb, int M,
+    int emb_in_lds, int A) {
+  const int Fg = NGF + A, nthr = blockDim.x;
+  float* const lds0 = f;
+  float (*w1)[H1][EMB + 1] = (float (*)[H1][EMB + 1])f;
+  f += 2 * H1 * (EMB + 1);
+  float (*wg)[64 + 1] = (float (*)[64 + 1])f;
+  f += GEMB * (64 + 1);
+  float* w2p = f;  f += A * W2P_LD;
+  float* ln_w = f; f += 64;
+  float* ln_b = f; f += 64;
+  float* bg = f;   f += 8;
+  float* b1p = f;  f += H1;
+  float* b2p = f;  f += 32;
+  float* b1v = f;  f += H1;
+  float* w2v = f;  f += H1;
+  float* b2v = f;  f += 8;
+  for (int i = threadIdx.x; i < H1 * EMB; i += nthr) {
+    w1[0][i / EMB][i % EMB] = head[4][i];
+    w1[1][i / EMB][i % EMB] = head[8][i];
+  }
+  for (int i = threadIdx.x; i < GEMB * Fg; i += nthr)
+    wg[i / Fg][i % Fg] = head[2][i];
+  for (int i = threadIdx.x; i < A * H1; i += nthr)
+    w2p[(i / H1) * W2P_LD + i % H1] = head[6][i];
+  for (int i = threadIdx.x; i < H1; i += nthr) {
+    b1p[i] = head[5][i];
+    b1v[i] = head[9][i];
+    w2v[i] = head[10][i];
+  }
+  for (int i = threadIdx.x; i < Fg; i += nthr) {
+    ln_w[i] = head[0][i];
+    ln_b[i] = head[1][i];
+  }
+  if (threadIdx.x < GEMB) bg[threadIdx.x] = head[3][threadIdx.x];
+  if (threadIdx.x < A) b2p[threadIdx.x] = head[7][threadIdx.x];
+  if (threadIdx.x == 0) b2v[0] = head[11][0];
+  const float* embt = model_emb;
+  if (emb_in_lds) {
+    for (int i = threadIdx.x; i < M * 16; i += nthr) f[i] = model_emb[i];
+    embt = f;
+    f += M * 16;
+  }
+  // the waves' regions hold f64 scratch: keep them 8-byte aligned
+  f = lds0 + (((f - lds0) + 1) & ~1L);
+  __syncthreads();
+  return {w1, wg, {ln_w, ln_b, bg, b1p, w2p, b2p, b1v, w2v, b2v, W2P_LD},
+          embt, f};
+}
+
+// One wave carries env row `b` from step t0[b] to its stop.  `ctr0` is word 0
+// of the Philox counter (the row for one policy, e = b % E for a population);
+// `mine` is the wave's own LDS region of R.wave_bytes.  No block barrier.
+template <bool POLICY>
+__device__ __forceinline__ void rollout_wave(
+    const EnvPtrs& P, const EnvDims& D, const RolloutArgs& R, int b,
+    unsigned ctr0, int lane, char* mine, const HeadLds& H) {
+  const int A = D.A, B = D.B, Fg = NGF + A, M = R.M;
   float* hand = (float*)mine;
   float* yln = hand + HAND;
   float* embw = yln + (POLICY ? YLN : 0);
@@ -172,15 +192,16 @@ env_rollout_kernel(EnvPtrs P, EnvDims D, RolloutArgs R) {
       double seq = 0.0;
       if (!POLICY && R.mode == ACCEPTABLE_JCT) seq = P.model_seq[mid];
       const ActorRowOut out = {
-          POLICY ? R.gfull + tb * Fg : nullptr,
-          POLICY ? R.lp_all + tb * A : nullptr,
-          POLICY ? R.logp + tb : nullptr, POLICY ? R.value + tb : nullptr,
+          R.gfull != nullptr ? R.gfull + tb * Fg : nullptr,
+          R.lp_all != nullptr ? R.lp_all + tb * A : nullptr,
+          R.logp != nullptr ? R.logp + tb : nullptr,
+          R.value != nullptr ? R.value + tb : nullptr,
           R.u != nullptr ? R.u + tb : nullptr};
       act = actor_row<POLICY>(
-          lane, (unsigned)b, hand, hand + NGF,
-          POLICY ? embt + (long)mid * 16 : nullptr, ksch, seq,
-          P.sch_acc + (long)b * D.SCH, D.SCH, w1s, wgs, yln, embw, h1, W, out,
-          A, R.mode, R.sip_ml_cap, R.seed_lo, R.seed_hi,
+          lane, ctr0, hand, hand + NGF,
+          POLICY ? H.embt + (long)mid * 16 : nullptr, ksch, seq,
+          P.sch_acc + (long)b * D.SCH, D.SCH, H.w1s, H.wgs, yln, embw, h1,
+          H.W, out, A, R.mode, R.sip_ml_cap, R.seed_lo, R.seed_hi,
           (unsigned)(step & 0xffffffffull), (unsigned)(step >> 32));
     }
     __builtin_amdgcn_wave_barrier();
@@ -215,18 +236,151 @@ env_rollout_kernel(EnvPtrs P, EnvDims D, RolloutArgs R) {
   if (lane == 0) { *stop_t = t; *stop_why = why; }
 }
 
+template <bool POLICY>
+__global__ void __launch_bounds__(WAVE * MAX_WPB)
+env_rollout_kernel(EnvPtrs P, EnvDims D, RolloutArgs R) {
+  extern __shared__ __align__(16) char lds[];
+  HeadLds H = {};
+  H.embt = R.model_emb;
+  H.waves = (float*)lds;
+  if constexpr (POLICY)
+    H = stage_head((float*)lds, R.head, R.model_emb, R.M, R.emb_in_lds, D.A);
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int b = blockIdx.x * (blockDim.x / WAVE) + wave;
+  if (b >= D.B) return;                     // no block barrier below
+  rollout_wave<POLICY>(P, D, R, b, (unsigned)b, lane,
+                       (char*)H.waves + (long)wave * R.wave_bytes, H);
+}
+
+// where member m's head and embedding table are
+struct PopArgs {
+  const float* pop;         // [P,n]
+  long n;
+  long off[12];             // head_fwd's parameter order, inside a pop row
+  int E;
+};
+
+// R.model_emb is model_emb_pop [P,M,16]; R.head is not used
+__global__ void __launch_bounds__(WAVE * MAX_WPB)
+env_rollout_pop_kernel(EnvPtrs P, EnvDims D, RolloutArgs R, PopArgs Q) {
+  extern __shared__ __align__(16) char lds[];
+  const int m = blockIdx.y;
+  const float* th = Q.pop + (long)m * Q.n;
+  const float* head[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) head[i] = th + Q.off[i];
+  const HeadLds H = stage_head((float*)lds, head,
+                               R.model_emb + (long)m * R.M * 16, R.M,
+                               R.emb_in_lds, D.A);
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int e = blockIdx.x * (blockDim.x / WAVE) + wave;
+  if (e >= Q.E) return;                     // no block barrier below
+  rollout_wave<true>(P, D, R, m * Q.E + e, (unsigned)e, lane,
+                     (char*)H.waves + (long)wave * R.wave_bytes, H);
+}
+
 // ---------------------------------------------------------------------------
-// host binding
+// host bindings
 // ---------------------------------------------------------------------------
 template <typename scalar>
-static scalar* row_ptr(const torch::Tensor& t, torch::ScalarType dt,
-                       int64_t numel, const char* what) {
+static scalar* row_ptr(const char* op, const torch::Tensor& t,
+                       torch::ScalarType dt, int64_t numel, const char* what) {
   if (t.numel() == 0) return nullptr;
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous() &&
-              t.numel() == numel, "env_rollout_batch: ", what,
+              t.numel() == numel, op, ": ", what,
               " must be a contiguous device tensor of ", numel,
               " elements of its dtype");
   return t.data_ptr<scalar>();
+}
+
+// What both bindings share: the engine's tensors and scalars, the control
+// arrays and the actor's scalars.
+static void rollout_setup(
+    const char* op, const std::vector<torch::Tensor>& T,
+    const std::vector<double>& fscal, const std::vector<int64_t>& iscal,
+    int64_t mode, int64_t sip_ml_cap, uint64_t seed, uint64_t step0,
+    int64_t steps, const torch::Tensor& t0, const torch::Tensor& stop,
+    EnvPtrs& P, EnvDims& D, RolloutArgs& R) {
+  env_unpack(T, fscal, iscal, P, D);
+  const int64_t B = D.B, A = D.A, Fg = NGF + A;
+  TORCH_CHECK(A >= 1 && A <= 32 && Fg <= 64,
+              op, ": needs 1 <= A <= 32 and 17 + A <= 64");
+  TORCH_CHECK(steps >= 1 && steps <= MAX_STEPS, op, ": steps "
+              "must be in [1, ", MAX_STEPS, "] per launch; chunk above it");
+  for (int k : {T_OBS_GF, T_OBS_MASK, T_OBS_MODEL, T_OBS_SCHED, T_DONE,
+                T_STATUS, T_REWARD, T_STEP_DONE, T_ACTIONS})
+    TORCH_CHECK(T[k].is_cuda() && T[k].is_contiguous() && T[k].size(0) == B,
+                op, ": engine tensor ", k, " is not [B, ...]");
+  TORCH_CHECK(T[T_OBS_MASK].numel() == B * A && T[T_OBS_GF].numel() == B * NGF,
+              op, ": obs_gf / obs_mask shape");
+  TORCH_CHECK(T[T_SCH_ACC].numel() == B * (int64_t)D.SCH,
+              op, ": sch_acc must be [B,SCH]");
+  auto i32 = [&](const torch::Tensor& t, int64_t n, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
+                t.is_contiguous() && t.numel() == n,
+                op, ": ", what, " must be a contiguous i32 "
+                "device tensor of ", n, " elements");
+    return t.data_ptr<int>();
+  };
+  R.t0 = i32(t0, B, "t0");
+  R.stop = i32(stop, 4 * B, "stop");
+  R.eng_actions = T[T_ACTIONS].data_ptr<int>();
+  R.T = (int)steps;
+  R.mode = (int)mode;
+  R.sip_ml_cap = (int)sip_ml_cap;
+  R.seed_lo = (unsigned)(seed & 0xffffffffu);
+  R.seed_hi = (unsigned)(seed >> 32);
+  R.step0 = step0;
+}
+
+// Envs per workgroup (at most `max_wpb`) and whether the embedding table is
+// staged, from the device's LDS budget; fills R.emb_in_lds / R.wave_bytes.
+// Returns {wpb, LDS bytes per workgroup}.
+static std::pair<int, size_t> rollout_lds_plan(
+    const char* op, bool policy, const EnvDims& D, RolloutArgs& R,
+    int max_wpb) {
+  size_t shared_bytes = 0, wave_bytes = HAND * sizeof(float);
+  if (policy) {
+    shared_bytes = (2 * H1 * (EMB + 1) + GEMB * (64 + 1) + D.A * W2P_LD +
+                    VEC_FLOATS) * sizeof(float);
+    // alignment pad in front of the waves' regions (they hold f64 scratch)
+    shared_bytes = (shared_bytes + 8 + 7) & ~(size_t)7;
+    wave_bytes += (YLN + EMBW + H1) * sizeof(float);
+  }
+  wave_bytes = (wave_bytes + env_step_scratch_bytes(D) + 7) & ~(size_t)7;
+  int dev = 0, budget = 0;
+  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
+              hipDeviceGetAttribute(&budget,
+                  hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess,
+              op, ": cannot read the LDS size");
+  int wpb = max_wpb;
+  while (wpb > 1 && shared_bytes + wpb * wave_bytes > (size_t)budget) --wpb;
+  TORCH_CHECK(shared_bytes + wpb * wave_bytes <= (size_t)budget,
+              op, ": one env needs ", shared_bytes + wave_bytes,
+              " bytes of LDS, the device has ", budget);
+  const size_t emb_bytes = (size_t)R.M * 16 * sizeof(float);
+  R.emb_in_lds = policy &&
+      shared_bytes + emb_bytes + wpb * wave_bytes <= (size_t)budget;
+  if (R.emb_in_lds) shared_bytes += emb_bytes;
+  R.wave_bytes = (int)wave_bytes;
+  return {wpb, shared_bytes + wpb * wave_bytes};
+}
+
+template <typename Kernel, typename... Args>
+static void rollout_launch(const char* op, Kernel kernel, dim3 grid, int wpb,
+                           size_t lds_bytes, Args... args) {
+  if (lds_bytes > 64 * 1024)
+    TORCH_CHECK(hipFuncSetAttribute(
+                    reinterpret_cast<const void*>(kernel),
+                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                    (int)lds_bytes) == hipSuccess,
+                op, ": cannot raise the dynamic LDS limit to ", lds_bytes);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(kernel, grid, dim3(WAVE * wpb), lds_bytes, stream,
+                     args...);
+  TORCH_CHECK(hipGetLastError() == hipSuccess, op, ": launch failed");
 }
 
 // Returns {envs per workgroup, LDS bytes per workgroup, 1 if the embedding
@@ -237,66 +391,40 @@ std::vector<int64_t> env_rollout_batch(
     std::vector<torch::Tensor> head, int64_t mode, int64_t sip_ml_cap,
     uint64_t seed, uint64_t step0, int64_t steps, torch::Tensor t0,
     torch::Tensor stop, std::vector<torch::Tensor> rows) {
+  const char* op = "env_rollout_batch";
   EnvPtrs P;
   EnvDims D;
-  env_unpack(T, fscal, iscal, P, D);
-  const int64_t B = D.B, A = D.A, Fg = NGF + A;
-  TORCH_CHECK(mode >= POLICY_GREEDY && mode <= ACCEPTABLE_JCT,
-              "env_rollout_batch: unknown mode ", mode);
-  TORCH_CHECK(A >= 1 && A <= 32 && Fg <= 64,
-              "env_rollout_batch: needs 1 <= A <= 32 and 17 + A <= 64");
-  TORCH_CHECK(steps >= 1 && steps <= MAX_STEPS, "env_rollout_batch: steps "
-              "must be in [1, ", MAX_STEPS, "] per launch; chunk above it");
-  TORCH_CHECK((int64_t)rows.size() == R_COUNT,
-              "env_rollout_batch: rows takes ", (int)R_COUNT, " tensors");
-  for (int k : {T_OBS_GF, T_OBS_MASK, T_OBS_MODEL, T_OBS_SCHED, T_DONE,
-                T_STATUS, T_REWARD, T_STEP_DONE, T_ACTIONS})
-    TORCH_CHECK(T[k].is_cuda() && T[k].is_contiguous() && T[k].size(0) == B,
-                "env_rollout_batch: engine tensor ", k, " is not [B, ...]");
-  TORCH_CHECK(T[T_OBS_MASK].numel() == B * A && T[T_OBS_GF].numel() == B * NGF,
-              "env_rollout_batch: obs_gf / obs_mask shape");
-  TORCH_CHECK(T[T_SCH_ACC].numel() == B * (int64_t)D.SCH,
-              "env_rollout_batch: sch_acc must be [B,SCH]");
-  auto i32 = [&](const torch::Tensor& t, int64_t n, const char* what) {
-    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
-                t.is_contiguous() && t.numel() == n,
-                "env_rollout_batch: ", what, " must be a contiguous i32 "
-                "device tensor of ", n, " elements");
-    return t.data_ptr<int>();
-  };
-
   RolloutArgs R = {};
-  R.t0 = i32(t0, B, "t0");
-  R.stop = i32(stop, 4 * B, "stop");
-  R.eng_actions = T[T_ACTIONS].data_ptr<int>();
-  R.T = (int)steps;
-  R.mode = (int)mode;
-  R.sip_ml_cap = (int)sip_ml_cap;
-  R.seed_lo = (unsigned)(seed & 0xffffffffu);
-  R.seed_hi = (unsigned)(seed >> 32);
-  R.step0 = step0;
+  TORCH_CHECK(mode >= POLICY_GREEDY && mode <= ACCEPTABLE_JCT,
+              op, ": unknown mode ", mode);
+  TORCH_CHECK((int64_t)rows.size() == R_COUNT,
+              op, ": rows takes ", (int)R_COUNT, " tensors");
+  rollout_setup(op, T, fscal, iscal, mode, sip_ml_cap, seed, step0, steps, t0,
+                stop, P, D, R);
+  const int64_t B = D.B, A = D.A, Fg = NGF + A;
   const bool policy = mode == POLICY_GREEDY || mode == POLICY_SAMPLE;
   const int64_t TB = steps * B;
-  R.u = row_ptr<float>(rows[R_U], torch::kFloat32, TB, "u");
-  R.rewards = row_ptr<float>(rows[R_REWARDS], torch::kFloat32, TB, "rewards");
-  R.actions = (long*)row_ptr<int64_t>(rows[R_ACTIONS], torch::kInt64, TB,
+  R.u = row_ptr<float>(op, rows[R_U], torch::kFloat32, TB, "u");
+  R.rewards = row_ptr<float>(op, rows[R_REWARDS], torch::kFloat32, TB,
+                             "rewards");
+  R.actions = (long*)row_ptr<int64_t>(op, rows[R_ACTIONS], torch::kInt64, TB,
                                       "actions");
-  R.model = (long*)row_ptr<int64_t>(rows[R_MODEL], torch::kInt64, TB, "model");
-  R.dones = row_ptr<uint8_t>(rows[R_DONES], torch::kUInt8, TB, "dones");
-  R.ret = row_ptr<double>(rows[R_RET], torch::kFloat64, B, "ret");
-  R.nlive = (long*)row_ptr<int64_t>(rows[R_NLIVE], torch::kInt64, B, "nlive");
-
-  size_t shared_bytes = 0, wave_bytes = HAND * sizeof(float);
+  R.model = (long*)row_ptr<int64_t>(op, rows[R_MODEL], torch::kInt64, TB,
+                                    "model");
+  R.dones = row_ptr<uint8_t>(op, rows[R_DONES], torch::kUInt8, TB, "dones");
+  R.ret = row_ptr<double>(op, rows[R_RET], torch::kFloat64, B, "ret");
+  R.nlive = (long*)row_ptr<int64_t>(op, rows[R_NLIVE], torch::kInt64, B,
+                                    "nlive");
   if (policy) {
     TORCH_CHECK(model_emb.is_cuda() && model_emb.dim() == 2 &&
                 model_emb.size(1) == 16 &&
                 model_emb.scalar_type() == torch::kFloat32 &&
                 model_emb.is_contiguous(),
-                "env_rollout_batch: model_emb must be a contiguous f32 "
+                op, ": model_emb must be a contiguous f32 "
                 "[M,16] device tensor");
     R.M = (int)model_emb.size(0);
     R.model_emb = model_emb.data_ptr<float>();
-    TORCH_CHECK(head.size() == 12, "env_rollout_batch: the policy modes take "
+    TORCH_CHECK(head.size() == 12, op, ": the policy modes take "
                 "head_fwd's 12 parameter tensors");
     const int64_t want[12] = {Fg, Fg, GEMB * Fg, GEMB, H1 * EMB, H1,
                               A * H1, A, H1 * EMB, H1, H1, 1};
@@ -304,63 +432,98 @@ std::vector<int64_t> env_rollout_batch(
       TORCH_CHECK(head[i].is_cuda() &&
                   head[i].scalar_type() == torch::kFloat32 &&
                   head[i].is_contiguous() && head[i].numel() == want[i],
-                  "env_rollout_batch: head[", i, "] must be a contiguous f32 "
+                  op, ": head[", i, "] must be a contiguous f32 "
                   "device tensor of ", want[i], " elements");
       R.head[i] = head[i].data_ptr<float>();
     }
     for (int k : {R_GFULL, R_LP_ALL, R_LOGP, R_VALUE})
-      TORCH_CHECK(rows[k].numel() > 0, "env_rollout_batch: the policy modes "
+      TORCH_CHECK(rows[k].numel() > 0, op, ": the policy modes "
                   "fill gfull, lp_all, logp and value");
-    R.gfull = row_ptr<float>(rows[R_GFULL], torch::kFloat32, TB * Fg, "gfull");
-    R.lp_all = row_ptr<float>(rows[R_LP_ALL], torch::kFloat32, TB * A,
+    R.gfull = row_ptr<float>(op, rows[R_GFULL], torch::kFloat32, TB * Fg,
+                             "gfull");
+    R.lp_all = row_ptr<float>(op, rows[R_LP_ALL], torch::kFloat32, TB * A,
                               "lp_all");
-    R.logp = row_ptr<float>(rows[R_LOGP], torch::kFloat32, TB, "logp");
-    R.value = row_ptr<float>(rows[R_VALUE], torch::kFloat32, TB, "value");
-    shared_bytes = (2 * H1 * (EMB + 1) + GEMB * (64 + 1) + A * W2P_LD +
-                    VEC_FLOATS) * sizeof(float);
-    // alignment pad in front of the waves' regions (they hold f64 scratch)
-    shared_bytes = (shared_bytes + 8 + 7) & ~(size_t)7;
-    wave_bytes += (YLN + EMBW + H1) * sizeof(float);
+    R.logp = row_ptr<float>(op, rows[R_LOGP], torch::kFloat32, TB, "logp");
+    R.value = row_ptr<float>(op, rows[R_VALUE], torch::kFloat32, TB, "value");
   } else {
     // M only bounds the model id: heuristics index model_seq alone
     R.M = (int)T[T_MODEL_SEQ].numel();
   }
-  wave_bytes = (wave_bytes + env_step_scratch_bytes(D) + 7) & ~(size_t)7;
   if (B == 0) return {0, 0, 0};
 
-  // envs per workgroup and the embedding table from the LDS budget
-  int dev = 0, budget = 0;
-  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess &&
-              hipDeviceGetAttribute(&budget,
-                  hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess,
-              "env_rollout_batch: cannot read the LDS size");
-  int wpb = MAX_WPB;
-  while (wpb > 1 && shared_bytes + wpb * wave_bytes > (size_t)budget) --wpb;
-  TORCH_CHECK(shared_bytes + wpb * wave_bytes <= (size_t)budget,
-              "env_rollout_batch: one env needs ", shared_bytes + wave_bytes,
-              " bytes of LDS, the device has ", budget);
-  const size_t emb_bytes = (size_t)R.M * 16 * sizeof(float);
-  R.emb_in_lds = policy &&
-      shared_bytes + emb_bytes + wpb * wave_bytes <= (size_t)budget;
-  if (R.emb_in_lds) shared_bytes += emb_bytes;
-  R.wave_bytes = (int)wave_bytes;
-  const size_t lds_bytes = shared_bytes + wpb * wave_bytes;
+  const auto [wpb, lds_bytes] = rollout_lds_plan(op, policy, D, R, MAX_WPB);
+  const dim3 grid((unsigned)((B + wpb - 1) / wpb));
+  if (policy)
+    rollout_launch(op, env_rollout_kernel<true>, grid, wpb, lds_bytes, P, D, R);
+  else
+    rollout_launch(op, env_rollout_kernel<false>, grid, wpb, lds_bytes, P, D,
+                   R);
+  return {wpb, (int64_t)lds_bytes, R.emb_in_lds};
+}
 
-  hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  const dim3 grid((unsigned)((B + wpb - 1) / wpb)), block(WAVE * wpb);
-  auto launch = [&](auto kernel) {
-    if (lds_bytes > 64 * 1024)
-      TORCH_CHECK(hipFuncSetAttribute(
-                      reinterpret_cast<const void*>(kernel),
-                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)lds_bytes) == hipSuccess,
-                  "env_rollout_batch: cannot raise the dynamic LDS limit to ",
-                  lds_bytes);
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, P, D, R);
-  };
-  if (policy) launch(env_rollout_kernel<true>);
-  else launch(env_rollout_kernel<false>);
-  TORCH_CHECK(hipGetLastError() == hipSuccess,
-              "env_rollout_batch: launch failed");
+// The population variant: member m = b / E of `pop` [P,n] plays engine rows
+// [mE, (m+1)E) with its own head (at `head_offs` inside its row) and its own
+// embedding table `model_emb_pop[m]`; the Philox index is e = b % E.  Keeps
+// `ret` / `nlive` [B] and, when given, the [steps,B] `actions` row.
+// `max_wpb` caps the envs per workgroup (the LDS budget may lower it).
+// Returns what env_rollout_batch returns.
+std::vector<int64_t> env_rollout_population(
+    std::vector<torch::Tensor> T, std::vector<double> fscal,
+    std::vector<int64_t> iscal, torch::Tensor pop,
+    torch::Tensor model_emb_pop, std::vector<int64_t> head_offs, int64_t E,
+    int64_t mode, uint64_t seed, uint64_t step0, int64_t steps,
+    torch::Tensor t0, torch::Tensor stop, torch::Tensor ret,
+    torch::Tensor nlive, torch::Tensor actions, int64_t max_wpb) {
+  const char* op = "env_rollout_population";
+  EnvPtrs P;
+  EnvDims D;
+  RolloutArgs R = {};
+  PopArgs Q = {};
+  TORCH_CHECK(mode == POLICY_GREEDY || mode == POLICY_SAMPLE,
+              op, ": mode must be 0 (greedy) or 1 (sample), not ", mode);
+  TORCH_CHECK(max_wpb >= 1 && max_wpb <= MAX_WPB,
+              op, ": max_wpb must be in [1, ", MAX_WPB, "]");
+  rollout_setup(op, T, fscal, iscal, mode, -1, seed, step0, steps, t0, stop,
+                P, D, R);
+  const int64_t B = D.B, A = D.A, Fg = NGF + A;
+  TORCH_CHECK(pop.dim() == 2 && pop.is_cuda() && pop.is_contiguous() &&
+              pop.scalar_type() == torch::kFloat32,
+              op, ": pop must be a contiguous f32 [P,n] device tensor");
+  const int64_t NP = pop.size(0), n = pop.size(1);
+  TORCH_CHECK(E >= 1 && NP >= 1 && NP <= 65535 && B == NP * E,
+              op, ": needs B == P * E with 1 <= P <= 65535 and E >= 1, got "
+              "B = ", B, ", P = ", NP, ", E = ", E);
+  TORCH_CHECK(model_emb_pop.is_cuda() && model_emb_pop.dim() == 3 &&
+              model_emb_pop.size(0) == NP && model_emb_pop.size(2) == 16 &&
+              model_emb_pop.scalar_type() == torch::kFloat32 &&
+              model_emb_pop.is_contiguous(),
+              op, ": model_emb_pop must be a contiguous f32 [P,M,16] device "
+              "tensor");
+  TORCH_CHECK(head_offs.size() == 12,
+              op, ": head_offs holds head_fwd's 12 row offsets");
+  const int64_t want[12] = {Fg, Fg, GEMB * Fg, GEMB, H1 * EMB, H1,
+                            A * H1, A, H1 * EMB, H1, H1, 1};
+  for (int i = 0; i < 12; ++i) {
+    TORCH_CHECK(head_offs[i] >= 0 && head_offs[i] + want[i] <= n,
+                op, ": head_offs[", i, "] = ", head_offs[i], " with ",
+                want[i], " elements leaves a pop row of ", n);
+    Q.off[i] = (long)head_offs[i];
+  }
+  Q.pop = pop.data_ptr<float>();
+  Q.n = (long)n;
+  Q.E = (int)E;
+  R.M = (int)model_emb_pop.size(1);
+  R.model_emb = model_emb_pop.data_ptr<float>();
+  TORCH_CHECK(ret.numel() == B && nlive.numel() == B,
+              op, ": ret and nlive are [B] accumulators");
+  R.ret = row_ptr<double>(op, ret, torch::kFloat64, B, "ret");
+  R.nlive = (long*)row_ptr<int64_t>(op, nlive, torch::kInt64, B, "nlive");
+  R.actions = (long*)row_ptr<int64_t>(op, actions, torch::kInt64, steps * B,
+                                      "actions");
+
+  const auto [wpb, lds_bytes] =
+      rollout_lds_plan(op, true, D, R, (int)max_wpb);
+  const dim3 grid((unsigned)((E + wpb - 1) / wpb), (unsigned)NP);
+  rollout_launch(op, env_rollout_pop_kernel, grid, wpb, lds_bytes, P, D, R, Q);
   return {wpb, (int64_t)lds_bytes, R.emb_in_lds};
 }

@@ -49,8 +49,16 @@ class ESConfig:
     # gt_pop_fwd_kernel (models.gnn.gnn_trunk_population); its embeddings
     # differ from the per-layer kernels' in the last bits
     population_trunk: str = "torch"
+    # population evaluator only.  "steps": one actor launch + one env step
+    # per step.  "fused" (opt-in): whole episodes in env_rollout_population
+    # launches (ops/hip/env_rollout.hip); same returns, bit for bit
+    population_rollout: str = "steps"
 
     def __post_init__(self):
+        if self.population_rollout not in POPULATION_ROLLOUTS:
+            raise ValueError("ESConfig.population_rollout must be one of "
+                             f"{POPULATION_ROLLOUTS}, not "
+                             f"{self.population_rollout!r}")
         if self.population_trunk not in POPULATION_TRUNKS:
             raise ValueError("ESConfig.population_trunk must be one of "
                              f"{POPULATION_TRUNKS}, not "
@@ -59,6 +67,7 @@ class ESConfig:
 
 EVALUATORS = ("sequential", "population")
 POPULATION_TRUNKS = ("torch", "fused")
+POPULATION_ROLLOUTS = ("steps", "fused")
 
 
 def centered_ranks(x: np.ndarray) -> np.ndarray:
@@ -134,7 +143,8 @@ class ESTrainer:
                 cfg.envs_per_member, eval_max_steps=cfg.eval_max_steps,
                 noise_seed=cfg.noise_seed,
                 deterministic=cfg.deterministic_eval,
-                trunk=cfg.population_trunk)
+                trunk=cfg.population_trunk,
+                rollout=cfg.population_rollout)
         return self._population
 
     def _get_flat(self) -> torch.Tensor:
@@ -198,6 +208,7 @@ class ESTrainer:
             "update_time_s": time.perf_counter() - t0,
             "evaluator": 1,
             "population_trunk": int(ev.fused_trunk),
+            "population_rollout": int(ev.fused_rollout),
             "eval_steps": res["eval_steps"],
             "truncated_envs": res["truncated_envs"],
             "tied_pairs": count_tied_pairs(fitness),

@@ -10,8 +10,10 @@ the perturbation alone.
 On a ``GpuEngine`` a generation is ``es_perturb`` (noise + population, one
 launch), ``P`` GNN forwards for the per-member embedding tables (or, with
 ``trunk="fused"``, one ``gt_pop_fwd_kernel`` launch for all of them), one
-``actor_population`` launch + one env step per step of the rollout, and
-``es_update`` (``ops/hip/es_population.hip``).  On a ``CpuEngine`` the
+``actor_population`` launch + one env step per step of the rollout (or, with
+``rollout="fused"``, whole episodes in ``env_rollout_population`` launches of
+up to ``fused_steps`` steps, bit-equal to the step loop), and ``es_update``
+(``ops/hip/es_population.hip``).  On a ``CpuEngine`` the
 reference functions below do the same work in numpy / torch.  Each backend is
 deterministic on its own; the two are not bit-equal to each other (``logf`` /
 ``sincosf`` differ in the last bits).
@@ -171,6 +173,9 @@ def act_population_reference(mode: int, obs_gf, obs_mask, obs_model,
 
 
 # ---------------------------------------------------------------------------
+POPULATION_ROLLOUTS = ("steps", "fused")
+
+
 class PopulationEvaluator:
     """Evaluates a whole ES population in one batched engine rollout.
 
@@ -183,7 +188,8 @@ class PopulationEvaluator:
     def __init__(self, vec_env, policy, perturbation_pairs: int,
                  envs_per_member: int, eval_max_steps: int = 100000,
                  noise_seed: int = 0, deterministic: bool = False,
-                 trunk: str = "torch"):
+                 trunk: str = "torch", rollout: str = "steps",
+                 fused_steps: int = 4096):
         if not getattr(vec_env, "supports_population_eval", False):
             raise TypeError("PopulationEvaluator needs an env with "
                             "supports_population_eval (EngineVectorEnv)")
@@ -210,6 +216,16 @@ class PopulationEvaluator:
         if trunk == "fused" and not getattr(policy.gnn, "_trunk_ok", False):
             raise ValueError("trunk='fused' is built for the tuned GNN shape "
                              "only (policy.gnn._trunk_ok)")
+        if rollout not in POPULATION_ROLLOUTS:
+            raise ValueError(f"rollout must be one of {POPULATION_ROLLOUTS}, "
+                             f"not {rollout!r}")
+        if int(fused_steps) < 1:
+            raise ValueError("fused_steps must be at least 1")
+        self.rollout_path = rollout
+        self.fused_steps = int(fused_steps)
+        # whole episodes in env_rollout_population launches (off the GPU
+        # "fused" is the step loop)
+        self.fused_rollout = rollout == "fused" and self.on_gpu
         self.trunk = trunk
         # the population kernel runs (off the GPU "fused" is the plain chain)
         self.fused_trunk = trunk == "fused" and self.on_gpu
@@ -337,7 +353,11 @@ class PopulationEvaluator:
         cap is not reached, actor -> step -> ``ret += reward where live``
         (f64 on the engine's device).  The Philox step counter is
         ``generation * eval_max_steps + t``: a function of the generation
-        alone, so a resumed run replays it."""
+        alone, so a resumed run replays it.  With ``rollout="fused"`` on a
+        GPU the loop runs inside ``env_rollout_population`` launches and the
+        result is bit-equal."""
+        if self.fused_rollout:
+            return self._rollout_fused(pop, model_emb_pop, generation)
         eng = self.eng
         dev = eng.T["reward"].device
         ret = torch.zeros(self.B, dtype=torch.float64, device=dev)
@@ -354,6 +374,28 @@ class PopulationEvaluator:
             nsteps += live.to(torch.int64)
             t += 1
         return ret, nsteps, t
+
+    def _rollout_fused(self, pop, model_emb_pop, generation: int):
+        """``rollout`` in chunks of at most ``fused_steps`` steps per launch
+        (``GpuEngine.rollout_population``), until every env is done or the
+        cap is reached."""
+        from ..cluster.gpu_engine import ROLLOUT_MAX_STEPS
+        eng = self.eng
+        ret = torch.zeros(self.B, dtype=torch.float64, device=self.device)
+        nsteps = torch.zeros(self.B, dtype=torch.int64, device=self.device)
+        step0 = int(generation) * self.eval_max_steps
+        t = played = 0
+        while t < self.eval_max_steps:
+            n = min(self.fused_steps, self.eval_max_steps - t,
+                    ROLLOUT_MAX_STEPS)
+            reached, ended = eng.rollout_population(
+                pop, model_emb_pop, self.head_offs, self.E, self.mode,
+                self.base_seed & _U64, step0 + t, n, ret, nsteps)
+            played = t + int(reached.max())
+            t += n
+            if ended.all():
+                break
+        return ret, nsteps, played
 
     def evaluate(self, pop: torch.Tensor, generation: int) -> Dict:
         """One generation's evaluation: ``fitness`` [P] (f64 mean over the

@@ -195,6 +195,7 @@ def build_trainer_from_config(cfg: dict, device=None):
             fragment_steps=algo.get("fragment_steps", 16),
             evaluator=algo.get("evaluator", "sequential"),
             population_trunk=algo.get("population_trunk", "torch"),
+            population_rollout=algo.get("population_rollout", "steps"),
             envs_per_member=algo.get("envs_per_member", 8),
             eval_max_steps=algo.get("eval_max_steps", 100000),
             noise_seed=algo.get("noise_seed", 0),

@@ -16,7 +16,7 @@ The timer is a host clock around a generation that ends in
 
 Usage: python scripts/es_population_bench.py [--pairs 16]
            [--envs-per-member 8] [--eval-max-steps 64] [--generations 3]
-           [--trunk {torch,fused}]
+           [--trunk {torch,fused}] [--rollout {steps,fused}]
 """
 import argparse
 import json
@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--trunk", choices=("torch", "fused"), default="torch",
                     help="ESConfig.population_trunk of the population "
+                         "trainer")
+    ap.add_argument("--rollout", choices=("steps", "fused"), default="steps",
+                    help="ESConfig.population_rollout of the population "
                          "trainer")
     ap.add_argument("--sampler", choices=("device", "fused"),
                     default="device",
@@ -86,7 +89,8 @@ def main():
             perturbation_pairs=K, fragment_steps=args.fragment_steps,
             evaluator=evaluator, envs_per_member=E,
             eval_max_steps=args.eval_max_steps,
-            population_trunk=args.trunk), device=dev)
+            population_trunk=args.trunk,
+            population_rollout=args.rollout), device=dev)
 
     trainers = {"sequential": trainer("sequential"),
                 "population": trainer("population")}
@@ -113,7 +117,8 @@ def main():
     out = {"pairs": K, "envs_per_member": E, "B": B,
            "eval_max_steps": args.eval_max_steps,
            "fragment_steps": args.fragment_steps,
-           "generations": args.generations, "trunk": args.trunk}
+           "generations": args.generations, "trunk": args.trunk,
+           "rollout": args.rollout}
     for name in trainers:
         t, n = float(np.median(times[name])), float(np.median(steps[name]))
         out[name] = {"ms_per_generation": t * 1e3,
