@@ -24,6 +24,7 @@ _SOURCES = [os.path.join(_HERE, "hip", "meanpool.hip"),
             os.path.join(_HERE, "hip", "meanpool_mfma.hip"),
             os.path.join(_HERE, "hip", "ppo_loss.hip"),
             os.path.join(_HERE, "hip", "vtrace_loss.hip"),
+            os.path.join(_HERE, "hip", "impala_head_step.hip"),
             os.path.join(_HERE, "hip", "dqn_loss.hip"),
             os.path.join(_HERE, "hip", "dqn_head_step.hip"),
             os.path.join(_HERE, "hip", "gnn_trunk.hip"),
@@ -41,7 +42,8 @@ _SOURCES = [os.path.join(_HERE, "hip", "meanpool.hip"),
 # older than one of them is stale
 _HEADERS = [os.path.join(_HERE, "hip", "cs_stage.h"),
             os.path.join(_HERE, "hip", "actor_row.h"),
-            os.path.join(_HERE, "hip", "env_step_body.h")]
+            os.path.join(_HERE, "hip", "env_step_body.h"),
+            os.path.join(_HERE, "hip", "vtrace_step.h")]
 
 
 def build_extensions(verbose: bool = False):

@@ -88,6 +88,18 @@ std::vector<torch::Tensor> impala_loss_bwd(
     torch::Tensor actions, torch::Tensor values, torch::Tensor vs,
     torch::Tensor pg_adv, torch::Tensor gl, int64_t T, int64_t N,
     double vf_coeff, double ent_coeff, bool drop_last);
+std::vector<torch::Tensor> impala_head_step_fwd(
+    torch::Tensor gfull, torch::Tensor model_ids, torch::Tensor actions,
+    torch::Tensor behaviour_logp, torch::Tensor rewards, torch::Tensor dones,
+    torch::Tensor bootstrap, torch::Tensor model_emb,
+    std::vector<torch::Tensor> head, int64_t T, int64_t N, double gamma,
+    double rho_clip, double pg_rho_clip, double c_clip, double vf_coeff,
+    double ent_coeff, bool drop_last, c10::optional<torch::Tensor> err_acc,
+    bool validate);
+std::vector<torch::Tensor> impala_head_step_bwd(
+    std::vector<torch::Tensor> saved, std::vector<torch::Tensor> head,
+    torch::Tensor gl, int64_t T, int64_t N, int64_t M, double vf_coeff,
+    double ent_coeff, bool drop_last);
 int64_t dqn_nstep_ingest(
     torch::Tensor gfull, torch::Tensor model_ids, torch::Tensor actions,
     torch::Tensor rewards, torch::Tensor dones,
@@ -223,6 +235,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused IMPALA loss: row softmax, V-trace scan, ordered reduction");
     m.def("impala_loss_bwd", &impala_loss_bwd,
           "analytic IMPALA loss backward");
+    m.def("impala_head_step_fwd", &impala_head_step_fwd,
+          "fused IMPALA actor-critic head step: head forward on MFMA row "
+          "tiles with the row epilogue, V-trace scan and ordered reduction");
+    m.def("impala_head_step_bwd", &impala_head_step_bwd,
+          "analytic backward of impala_head_step_fwd into the head tensors "
+          "and model_emb (chunked MFMA weight-grad tiles)");
     m.def("dqn_nstep_ingest", &dqn_nstep_ingest,
           "n-step transitions of a [T, N] fragment written into the replay "
           "ring, bit-equal to nstep_transitions_reference");

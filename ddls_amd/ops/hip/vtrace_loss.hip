@@ -20,13 +20,15 @@
 // Layout is [T, N] row-major (sample row i = t*N + n), the order
 // EngineVectorEnv.rollout returns.
 //
-// Bit contract: vtrace_step() below performs each f32 add/sub/mul singly and
-// in exactly the order rl/impala.py::vtrace_targets evaluates them (no FMA
-// contraction), so vtrace_scan equals vtrace_targets bit for bit.
+// Bit contract: vtrace_step() (vtrace_step.h) performs each f32 add/sub/mul
+// singly and in exactly the order rl/impala.py::vtrace_targets evaluates
+// them (no FMA contraction), so vtrace_scan equals vtrace_targets bit for bit.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <vector>
+
+#include "vtrace_step.h"
 
 #define WAVE 64
 #define WAVES 4
@@ -51,32 +53,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int off = 32; off > 0; off >>= 1)
         v += __shfl_down(v, off, WAVE);
     return v;   // valid on lane 0
-}
-
-// One timestep of the recurrence for one env column.  v_next / vs_next are
-// V(x_{t+1}) / vs_{t+1}, with the bootstrap value standing in at t = T-1.
-// acc carries vs_{t+1} - V(x_{t+1}) in and vs_t - V(x_t) out.
-__device__ __forceinline__ void vtrace_step(float r, float done, float v,
-                                            float v_next, float vs_next,
-                                            float rho, float c, float gamma,
-                                            float& acc, float& vs_out,
-                                            float& pg_out) {
-#pragma clang fp contract(off)
-    const float nonterminal = 1.0f - done;
-    const float vtp1 = v_next * nonterminal;
-    const float gv = gamma * vtp1;
-    const float rgv = r + gv;
-    const float td = rgv - v;
-    const float delta = rho * td;
-    const float gc = gamma * c;
-    const float gcn = gc * nonterminal;
-    const float carry = gcn * acc;
-    acc = delta + carry;
-    vs_out = v + acc;
-    const float vsn = vs_next * nonterminal;
-    const float gvs = gamma * vsn;
-    const float rgvs = r + gvs;
-    pg_out = rgvs - v;
 }
 
 // one lane per env column, t = T-1 .. 0; row t is read coalesced across lanes

@@ -23,6 +23,16 @@ the host and evaluates the loss as a torch autograd chain.  ``"device"``
 trains from the flat device tensors of ``rollout(device_resident=True)``: the
 forward never touches ``data["obs"]``, and on a GPU the loss is the fused
 kernels of ``ops/hip/vtrace_loss.hip`` with one D2H for the stats.
+
+Two opt-in switches act on the device learner only.
+``ImpalaConfig.trunk_step="fused"`` takes the per-model embeddings from the
+fused GNN trunk kernels (``models.gnn.gnn_trunk``).
+``ImpalaConfig.head_step="fused"`` replaces everything between the rollout
+tensors and the loss (LN, graph Linear, gather, both branches, mask, V-trace
+loss and their backward) with the kernels of ``ops/hip/impala_head_step.hip``:
+two launches forward, two backward.  On CPU tensors (the CpuEngine backend)
+it is ``impala_head_step_reference``, the same torch expressions as the
+default path.
 """
 from __future__ import annotations
 
@@ -59,12 +69,24 @@ class ImpalaConfig:
     # rl/rollout.py ROLLOUT_SAMPLERS); forwarded only when it is not "torch"
     # and the env advertises supports_device_sampler
     rollout_sampler: str = "torch"
+    # device learner only.  "fused": the head forward, the V-trace loss and
+    # their backward are the kernels of ops/hip/impala_head_step.hip
+    # (policy._fused_head_ok shapes only)
+    head_step: str = "torch"
+    # device learner only.  "fused": the GNN trunk forward and backward are
+    # the kernels of ops/hip/gnn_trunk.hip (policy.gnn._trunk_ok shapes only)
+    trunk_step: str = "torch"
 
     def __post_init__(self):
         check_rollout_sampler(self.rollout_sampler, "ImpalaConfig")
+        for name in ("head_step", "trunk_step"):
+            if getattr(self, name) not in STEP_MODES:
+                raise ValueError(f"ImpalaConfig.{name} must be 'torch' or "
+                                 f"'fused', not {getattr(self, name)!r}")
 
 
 LEARNERS = ("torch", "device")
+STEP_MODES = ("torch", "fused")
 
 
 def vtrace_targets(rewards, dones, values, bootstrap, rho, c, gamma):
@@ -160,6 +182,64 @@ class _ImpalaLossFn(torch.autograd.Function):
         return (glogits, gvalues) + (None,) * 14
 
 
+def impala_head_step_reference(gfull, model_ids, actions, behaviour_logp,
+                               rewards, dones, bootstrap, model_emb, head,
+                               T, N, cfg):
+    """One step of the actor-critic head over the flat [T*N] rollout tensors
+    as a plain torch chain, in the dtype of its inputs: ``_heads_functional``
+    on the 12 ``head`` tensors (``head_params`` order), then
+    ``impala_loss_reference``.  Differentiable in ``model_emb`` and ``head``.
+    Returns (loss, stats[5] in STAT_KEYS order)."""
+    from .dqn import _heads_functional   # rl/dqn.py imports this module
+    logits, values = _heads_functional(head, model_emb, gfull, model_ids)
+    loss, st = impala_loss_reference(
+        logits, values, actions, behaviour_logp, rewards.reshape(T, N),
+        dones, bootstrap, cfg)
+    return loss, torch.stack([st[k] for k in STAT_KEYS])
+
+
+class _ImpalaHeadStepFn(torch.autograd.Function):
+    """Fused actor-critic head step (ops/hip/impala_head_step.hip): two
+    launches forward, two backward.  ``model_emb`` and the 12 ``head``
+    tensors take a gradient, everything else is a constant.  Returns (loss,
+    stats[5] in STAT_KEYS order).  ``err`` (int32 [1], optional) is OR-ed
+    with the device validation flag so a caller can read it with its other
+    results; without it the call validates at once, which costs a host
+    sync."""
+
+    @staticmethod
+    def forward(ctx, gfull, model_ids, actions, behaviour_logp, rewards,
+                dones, bootstrap, model_emb, T, N, gamma, rho_clip,
+                pg_rho_clip, c_clip, vf_coeff, ent_coeff, drop_last, err,
+                *head):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        head_c = [t.detach().contiguous() for t in head]
+        out = ext.impala_head_step_fwd(
+            gfull, model_ids, actions, behaviour_logp, rewards, dones,
+            bootstrap, model_emb.detach().contiguous(), head_c, int(T),
+            int(N), float(gamma), float(rho_clip), float(pg_rho_clip),
+            float(c_clip), float(vf_coeff), float(ent_coeff),
+            bool(drop_last), err, err is None)
+        loss, stats = out[0], out[1]
+        ctx.save_for_backward(*out[3:15], *head_c)
+        ctx.consts = (int(T), int(N), model_emb.shape[0], float(vf_coeff),
+                      float(ent_coeff), bool(drop_last))
+        ctx.mark_non_differentiable(stats)
+        return loss.reshape(()), stats
+
+    @staticmethod
+    def backward(ctx, gl, _gstats):
+        from .. import ops as hip_ops
+        ext = hip_ops.get_extension(required=True)
+        saved, head = ctx.saved_tensors[:12], ctx.saved_tensors[12:]
+        T, N, M, vf_coeff, ent_coeff, drop_last = ctx.consts
+        grads = ext.impala_head_step_bwd(
+            list(saved), list(head), gl.reshape(1).contiguous(), T, N, M,
+            vf_coeff, ent_coeff, drop_last)
+        return (None,) * 7 + (grads[12],) + (None,) * 10 + tuple(grads[:12])
+
+
 class ImpalaTrainer:
     """Same trainer-facing interface as PPOTrainer (train/state_dict/...)."""
 
@@ -171,6 +251,19 @@ class ImpalaTrainer:
             raise ValueError("ImpalaConfig.learner must be 'torch' or "
                              f"'device', not {self.config.learner!r}")
         self._learner_warned = False
+        # getattr: subclasses pass configs without these switches
+        self._head_mode = getattr(self.config, "head_step", "torch")
+        self._trunk_mode = getattr(self.config, "trunk_step", "torch")
+        if self._head_mode == "fused" and not getattr(
+                policy, "_fused_head_ok", False):
+            raise ValueError("ImpalaConfig.head_step='fused' serves the "
+                             "fused head shapes only (policy._fused_head_ok)")
+        if self._trunk_mode == "fused" and not getattr(
+                getattr(policy, "gnn", None), "_trunk_ok", False):
+            raise ValueError("ImpalaConfig.trunk_step='fused' serves the "
+                             "tuned GNN shape only (policy.gnn._trunk_ok)")
+        # the head step kernels' validation flag, read with the stats
+        self._head_err = None
         self.device = device or torch.device(
             "cuda" if torch.cuda.is_available() else "cpu")
         self.policy = policy.to(self.device)
@@ -273,13 +366,43 @@ class ImpalaTrainer:
         return self.policy.forward_flat(
             inputs["batch"], inputs["graph_features"], inputs["action_mask"])
 
+    def _policy_model_emb(self):
+        """The policy's per-model GNN embeddings of the static models
+        batch."""
+        from ..models.gnn import gnn_trunk, graph_mean
+        mb_static = self.env._models_batch
+        if self._trunk_mode == "fused":
+            return gnn_trunk(self.policy.gnn, mb_static)
+        node_emb = self.policy.gnn(mb_static)
+        return graph_mean(node_emb, mb_static)
+
+    def _head_step_device(self, data: Dict):
+        """``head_step="fused"``: the kernels on a GPU (``_head_err``
+        collects their validation flag), ``impala_head_step_reference`` on
+        CPU tensors."""
+        from .dqn import head_tensors
+        cfg = self.config
+        T, N = data["rewards"].shape
+        model_emb = self._policy_model_emb()
+        args = (data["gfull_dev"], data["model_ids_dev"], data["actions_dev"],
+                data["logp_dev"], data["rewards_dev"], data["dones_dev"],
+                data["bootstrap_dev"], model_emb)
+        if model_emb.is_cuda:
+            if self._head_err is None:
+                self._head_err = torch.zeros(1, dtype=torch.int32,
+                                             device=model_emb.device)
+            return _ImpalaHeadStepFn.apply(
+                *args, T, N, cfg.gamma, cfg.rho_clip, cfg.pg_rho_clip,
+                cfg.c_clip, cfg.vf_loss_coeff, cfg.entropy_coeff,
+                cfg.vtrace_drop_last_ts, self._head_err,
+                *head_tensors(self.policy))
+        return impala_head_step_reference(
+            *args, head_tensors(self.policy), T, N, cfg)
+
     def _forward_device(self, data: Dict):
         """Differentiable forward from the flat device tensors of a
         device-resident rollout; never indexes ``data["obs"]``."""
-        from ..models.gnn import graph_mean
-        mb_static = self.env._models_batch
-        node_emb = self.policy.gnn(mb_static)
-        model_emb = graph_mean(node_emb, mb_static)
+        model_emb = self._policy_model_emb()
         gfull = data["gfull_dev"]
         graph_emb = self.policy.graph_module(gfull)
         final = torch.cat([model_emb[data["model_ids_dev"]], graph_emb],
@@ -297,6 +420,8 @@ class ImpalaTrainer:
         (the CpuEngine backend)."""
         cfg = self.config
         T, N = data["rewards"].shape
+        if self._head_mode == "fused":
+            return self._head_step_device(data)
         logits, values = self._forward_device(data)
         args = (logits, values, data["actions_dev"], data["logp_dev"])
         if logits.is_cuda:
@@ -340,12 +465,26 @@ class ImpalaTrainer:
             torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
                                            cfg.grad_clip)
         self.optimizer.step()
-        if on_device:
+        if on_device and self._head_err is not None:
+            # one D2H for the five stats and the kernels' validation flag
+            out = torch.cat([stats_t.detach(),
+                             self._head_err.to(stats_t.dtype)]).tolist()
+            if out[len(STAT_KEYS)] != 0.0:
+                self._head_err.zero_()
+                raise RuntimeError(
+                    "impala_head_step: the rollout named a model id outside "
+                    "[0, M) or an action outside [0, A)")
+            stats = dict(zip(STAT_KEYS, out))
+        elif on_device:
             # one D2H for all five stats
             stats = dict(zip(STAT_KEYS, stats_t.detach().tolist()))
         else:
             stats = {k: float(stats_d[k].item()) for k in STAT_KEYS}
         stats["learner"] = 1 if on_device else 0
+        if on_device:
+            on_gpu = stats_t.is_cuda
+            stats["head_step"] = int(self._head_mode == "fused" and on_gpu)
+            stats["trunk_step"] = int(self._trunk_mode == "fused" and on_gpu)
         return stats
 
     # ------------------------------------------------------------------

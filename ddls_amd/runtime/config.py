@@ -248,6 +248,8 @@ def build_trainer_from_config(cfg: dict, device=None):
             train_batch_size=algo.get("train_batch_size", 4000),
             vtrace_drop_last_ts=algo.get("vtrace_drop_last_ts", True),
             learner=str(algo.get("learner", "torch")),
+            head_step=str(algo.get("head_step", "torch")),
+            trunk_step=str(algo.get("trunk_step", "torch")),
             rollout_sampler=str(algo.get("rollout_sampler", "torch")))
         return ImpalaTrainer(venv, policy, imp_cfg, device=device)
     ppo_cfg = PPOConfig(

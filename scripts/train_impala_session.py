@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """IMPALA (V-trace) / PG training session on the GPU-resident env engine —
 demonstrates the non-PPO algorithms end-to-end on the flagship stack.
-Env: ALGO=impala|pg ITERS=N OUT=dir LEARNER=torch|device (IMPALA only);
-EVAL=0 skips the greedy evaluation after training."""
+Env: ALGO=impala|pg ITERS=N OUT=dir LEARNER=torch|device and, for the device
+learner, HEAD_STEP=torch|fused TRUNK_STEP=torch|fused (IMPALA only); EVAL=0 skips the greedy evaluation after training."""
 import json
 import os
 import sys
@@ -21,6 +21,8 @@ ALGO = os.environ.get("ALGO", "impala")
 ITERS = int(os.environ.get("ITERS", "40"))
 OUT = os.environ.get("OUT", f"gpurun_out/{ALGO}_session")
 LEARNER = os.environ.get("LEARNER", "torch")
+HEAD_STEP = os.environ.get("HEAD_STEP", "torch")
+TRUNK_STEP = os.environ.get("TRUNK_STEP", "torch")
 
 
 def main():
@@ -36,7 +38,9 @@ def main():
     else:
         tr = ImpalaTrainer(venv, policy,
                            ImpalaConfig(train_batch_size=4096,
-                                        learner=LEARNER), device=dev)
+                                        learner=LEARNER,
+                                        head_step=HEAD_STEP,
+                                        trunk_step=TRUNK_STEP), device=dev)
     log = []
     t0 = time.time()
     for i in range(ITERS):
@@ -57,7 +61,8 @@ def main():
     # how an iteration divides (the first one carries warm-up, leave it out)
     tail = log[1:] or log
     print(json.dumps({
-        "algo": ALGO, "learner": LEARNER, "iters": ITERS,
+        "algo": ALGO, "learner": LEARNER, "head_step": HEAD_STEP,
+        "trunk_step": TRUNK_STEP, "iters": ITERS,
         "env_steps_per_s": tr.total_env_steps / dt,
         "rollout_ms": 1e3 * sum(r["rollout_time_s"] for r in tail) / len(tail),
         "update_ms": 1e3 * sum(r["update_time_s"] for r in tail) / len(tail),
