@@ -28,6 +28,7 @@ _SOURCES = [os.path.join(_HERE, "hip", "meanpool.hip"),
             os.path.join(_HERE, "hip", "dqn_loss.hip"),
             os.path.join(_HERE, "hip", "dqn_head_step.hip"),
             os.path.join(_HERE, "hip", "gnn_trunk.hip"),
+            os.path.join(_HERE, "hip", "learner_tail.hip"),
             os.path.join(_HERE, "hip", "per_replay.hip"),
             os.path.join(_HERE, "hip", "policy_head.hip"),
             os.path.join(_HERE, "hip", "lookahead.hip"),

@@ -140,6 +140,15 @@ std::vector<torch::Tensor> gnn_trunk_bwd(torch::Tensor gemb,
 torch::Tensor gnn_trunk_population_fwd(torch::Tensor z, torch::Tensor e,
                                        std::vector<torch::Tensor> plan,
                                        torch::Tensor pop, int64_t off);
+void learner_tail(std::vector<torch::Tensor> params,
+                  std::vector<torch::Tensor> grads,
+                  std::vector<torch::Tensor> exp_avg,
+                  std::vector<torch::Tensor> exp_avg_sq, torch::Tensor step_t,
+                  torch::Tensor stats_out, c10::optional<torch::Tensor> acc,
+                  c10::optional<torch::Tensor> stats_in, double lr,
+                  double beta1, double beta2, double eps, double max_norm,
+                  bool zero_grads);
+std::vector<int64_t> learner_tail_limits();
 void per_ingest(torch::Tensor tree_sum, torch::Tensor tree_min,
                 torch::Tensor max_prio, int64_t start, int64_t count,
                 int64_t capacity, double alpha);
@@ -267,6 +276,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "GNN trunk forward of P population members in one launch, one "
           "workgroup per (graph, member), weights read from pop[m, off:]; "
           "returns model_emb [P, G, 16]");
+    m.def("learner_tail", &learner_tail,
+          "the device learners' optimiser tail over lists of tensors: global "
+          "grad norm, clip, torch's Adam update, step count and acc += "
+          "stats_in; one launch up to learner_tail_limits()[1] elements, two "
+          "above");
+    m.def("learner_tail_limits", &learner_tail_limits,
+          "learner_tail's tensor capacity, its largest one-launch total and "
+          "the elements per block of its two-launch path");
     m.def("per_ingest", &per_ingest,
           "prioritized replay: new slots enter the sum/min trees at "
           "max_prio^alpha");

@@ -47,6 +47,12 @@ forward and its autograd backward, ``graph_mean(policy.gnn(models_batch))``,
 by the kernels of ``ops/hip/gnn_trunk.hip`` (``models.gnn.gnn_trunk``): one
 launch forward and two backward per minibatch, and one forward per update for
 the target net.  It combines with either ``head_step``.
+
+``DQNConfig.optimizer_step="fused"`` (device learner only) replaces what
+follows the gradient all-reduce in a minibatch, ``clip_grad_norm_`` +
+``optimizer.step()`` + the stats accumulation, by the one launch of
+``ops/hip/learner_tail.hip`` (``rl/learner_tail.py``) over the same Adam
+state.  It combines with every ``head_step`` / ``trunk_step``.
 """
 from __future__ import annotations
 
@@ -65,6 +71,7 @@ from .rollout import CompactObs, check_rollout_sampler
 
 HEAD_STEPS = ("torch", "fused")
 TRUNK_STEPS = ("torch", "fused")
+OPTIMIZER_STEPS = ("torch", "fused")
 
 
 @dataclass
@@ -102,11 +109,18 @@ class DQNConfig:
     # per-layer kernels under autograd.  "fused": the kernels of
     # ops/hip/gnn_trunk.hip (policy.gnn._trunk_ok shapes only)
     trunk_step: str = "torch"
+    # the device learner's optimiser tail.  "torch": clip_grad_norm_ +
+    # optimizer.step() + acc += stats.  "fused": the one launch of
+    # ops/hip/learner_tail.hip (rl/learner_tail.py) per minibatch
+    optimizer_step: str = "torch"
     # see ImpalaConfig.rollout_sampler
     rollout_sampler: str = "torch"
 
     def __post_init__(self):
         check_rollout_sampler(self.rollout_sampler, "DQNConfig")
+        if self.optimizer_step not in OPTIMIZER_STEPS:
+            raise ValueError("DQNConfig.optimizer_step must be 'torch' or "
+                             f"'fused', not {self.optimizer_step!r}")
         if self.trunk_step not in TRUNK_STEPS:
             raise ValueError("DQNConfig.trunk_step must be 'torch' or "
                              f"'fused', not {self.trunk_step!r}")
@@ -386,6 +400,7 @@ class DQNTrainer(ImpalaTrainer):
         self.config = cfg
         self.optimizer = torch.optim.Adam(self.policy.parameters(),
                                           lr=cfg.lr, foreach=True)
+        self._tail = self._make_tail()
         import copy
         self.target = copy.deepcopy(self.policy).to(self.device)
         self.target.eval()
@@ -526,6 +541,19 @@ class DQNTrainer(ImpalaTrainer):
             ring, idx, model_emb, target_emb, head_tensors(self.policy),
             head_params(self.target), *args, weights=weights)
 
+    def _optimizer_tail(self, stats_t, acc) -> bool:
+        """What follows ``all_reduce_gradients`` in a device minibatch: clip,
+        Adam step and ``acc += stats_t`` (``acc`` may be a slice).  True when
+        the ``optimizer_step="fused"`` kernel did all three."""
+        if self._tail is not None:
+            return self._tail.step(stats_t, acc)
+        if self.config.grad_clip is not None:
+            torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
+                                           self.config.grad_clip)
+        self.optimizer.step()
+        acc += stats_t.detach()
+        return False
+
     def _check_head_step(self, flag: float):
         """``flag``: the kernels' validation flag, read with the stats."""
         if flag != 0:
@@ -549,6 +577,7 @@ class DQNTrainer(ImpalaTrainer):
             return self._update_device_prioritized(data)
         stats = {k: 0.0 for k in STAT_KEYS}
         fused = cfg.head_step == "fused"
+        tail_ran = False
         if len(replay) >= cfg.learning_starts and cfg.num_sgd_iter > 0:
             rng = np.random.RandomState(self.iteration)
             # the torch learner's draws, uploaded once
@@ -571,11 +600,7 @@ class DQNTrainer(ImpalaTrainer):
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
                 all_reduce_gradients(self.policy.parameters())
-                if cfg.grad_clip is not None:
-                    torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
-                                                   cfg.grad_clip)
-                self.optimizer.step()
-                acc += stats_t.detach()
+                tail_ran = self._optimizer_tail(stats_t, acc)
             # one D2H for all stats of all minibatches
             acc = acc / cfg.num_sgd_iter
             if err is not None:
@@ -588,6 +613,7 @@ class DQNTrainer(ImpalaTrainer):
         stats["learner"] = 1
         stats["head_step"] = int(fused and replay.device.type == "cuda")
         stats["trunk_step"] = self._trunk_stat()
+        stats["optimizer_step"] = int(tail_ran)
         self._sync_target(data)
         return stats
 
@@ -601,6 +627,7 @@ class DQNTrainer(ImpalaTrainer):
         keys = STAT_KEYS + PER_STAT_KEYS
         stats = {k: 0.0 for k in keys}
         fused = cfg.head_step == "fused"
+        tail_ran = False
         if len(replay) >= cfg.learning_starts and cfg.num_sgd_iter > 0:
             rng = np.random.RandomState(self.iteration)
             # the torch learner's uniforms, uploaded once
@@ -623,12 +650,9 @@ class DQNTrainer(ImpalaTrainer):
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
                 all_reduce_gradients(self.policy.parameters())
-                if cfg.grad_clip is not None:
-                    torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
-                                                   cfg.grad_clip)
-                self.optimizer.step()
+                tail_ran = self._optimizer_tail(stats_t,
+                                                acc[:len(STAT_KEYS)])
                 replay.update_priorities(idx, td_abs)
-                acc[:len(STAT_KEYS)] += stats_t.detach()
                 acc[len(STAT_KEYS)] += weight.mean()
             # one D2H for all stats of all minibatches and max_prio
             parts = [acc.double() / cfg.num_sgd_iter, replay.max_prio]
@@ -642,6 +666,7 @@ class DQNTrainer(ImpalaTrainer):
         stats["learner"] = 1
         stats["head_step"] = int(fused and replay.device.type == "cuda")
         stats["trunk_step"] = self._trunk_stat()
+        stats["optimizer_step"] = int(tail_ran)
         self._sync_target(data)
         return stats
 

@@ -24,7 +24,10 @@ trains from the flat device tensors of ``rollout(device_resident=True)``: the
 forward never touches ``data["obs"]``, and on a GPU the loss is the fused
 kernels of ``ops/hip/vtrace_loss.hip`` with one D2H for the stats.
 
-Two opt-in switches act on the device learner only.
+Three opt-in switches act on the device learner only.
+``ImpalaConfig.optimizer_step="fused"`` replaces ``clip_grad_norm_`` +
+``optimizer.step()`` by the one launch of ``ops/hip/learner_tail.hip``
+(``rl/learner_tail.py``) over the same Adam state.
 ``ImpalaConfig.trunk_step="fused"`` takes the per-model embeddings from the
 fused GNN trunk kernels (``models.gnn.gnn_trunk``).
 ``ImpalaConfig.head_step="fused"`` replaces everything between the rollout
@@ -76,10 +79,14 @@ class ImpalaConfig:
     # device learner only.  "fused": the GNN trunk forward and backward are
     # the kernels of ops/hip/gnn_trunk.hip (policy.gnn._trunk_ok shapes only)
     trunk_step: str = "torch"
+    # device learner only.  "fused": grad clip + Adam step are the one launch
+    # of ops/hip/learner_tail.hip (rl/learner_tail.py) over the optimizer's
+    # own state, in place of clip_grad_norm_ + optimizer.step()
+    optimizer_step: str = "torch"
 
     def __post_init__(self):
         check_rollout_sampler(self.rollout_sampler, "ImpalaConfig")
-        for name in ("head_step", "trunk_step"):
+        for name in ("head_step", "trunk_step", "optimizer_step"):
             if getattr(self, name) not in STEP_MODES:
                 raise ValueError(f"ImpalaConfig.{name} must be 'torch' or "
                                  f"'fused', not {getattr(self, name)!r}")
@@ -269,9 +276,20 @@ class ImpalaTrainer:
         self.policy = policy.to(self.device)
         self.optimizer = torch.optim.Adam(self.policy.parameters(),
                                           lr=self.config.lr, foreach=True)
+        self._tail = self._make_tail()
         self.obs = self.env.reset()
         self.total_env_steps = 0
         self.iteration = 0
+
+    def _make_tail(self):
+        """The ``LearnerTail`` over ``self.optimizer`` with
+        ``optimizer_step="fused"``, else None.  Read with getattr: subclasses
+        pass configs without the switch."""
+        if getattr(self.config, "optimizer_step", "torch") != "fused":
+            return None
+        from .learner_tail import LearnerTail
+        return LearnerTail(self.optimizer, self.policy.parameters(),
+                           self.config.grad_clip)
 
     # ------------------------------------------------------------------
     @torch.no_grad()
@@ -461,10 +479,14 @@ class ImpalaTrainer:
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         all_reduce_gradients(self.policy.parameters())
-        if cfg.grad_clip is not None:
-            torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
-                                           cfg.grad_clip)
-        self.optimizer.step()
+        tail_ran = False
+        if on_device and self._tail is not None:
+            tail_ran = self._tail.step()
+        else:
+            if cfg.grad_clip is not None:
+                torch.nn.utils.clip_grad_norm_(self.policy.parameters(),
+                                               cfg.grad_clip)
+            self.optimizer.step()
         if on_device and self._head_err is not None:
             # one D2H for the five stats and the kernels' validation flag
             out = torch.cat([stats_t.detach(),
@@ -485,6 +507,7 @@ class ImpalaTrainer:
             on_gpu = stats_t.is_cuda
             stats["head_step"] = int(self._head_mode == "fused" and on_gpu)
             stats["trunk_step"] = int(self._trunk_mode == "fused" and on_gpu)
+            stats["optimizer_step"] = int(tail_ran)
         return stats
 
     # ------------------------------------------------------------------
@@ -517,6 +540,8 @@ class ImpalaTrainer:
 
     # ------------------------------------------------------------------
     def state_dict(self) -> Dict:
+        if self._tail is not None:
+            self._tail.sync_steps()
         return {"policy": self.policy.state_dict(),
                 "optimizer": self.optimizer.state_dict(),
                 "iteration": self.iteration,
@@ -526,5 +551,7 @@ class ImpalaTrainer:
     def load_state_dict(self, state: Dict):
         self.policy.load_state_dict(state["policy"])
         self.optimizer.load_state_dict(state["optimizer"])
+        if self._tail is not None:
+            self._tail.load_steps()
         self.iteration = state.get("iteration", 0)
         self.total_env_steps = state.get("total_env_steps", 0)

@@ -218,6 +218,7 @@ def build_trainer_from_config(cfg: dict, device=None):
             learner=str(algo.get("learner", "torch")),
             head_step=str(algo.get("head_step", "torch")),
             trunk_step=str(algo.get("trunk_step", "torch")),
+            optimizer_step=str(algo.get("optimizer_step", "torch")),
             rollout_sampler=str(algo.get("rollout_sampler", "torch")),
             prioritized_replay=bool(algo.get("prioritized_replay", False)),
             prioritized_replay_alpha=algo.get(
@@ -250,6 +251,7 @@ def build_trainer_from_config(cfg: dict, device=None):
             learner=str(algo.get("learner", "torch")),
             head_step=str(algo.get("head_step", "torch")),
             trunk_step=str(algo.get("trunk_step", "torch")),
+            optimizer_step=str(algo.get("optimizer_step", "torch")),
             rollout_sampler=str(algo.get("rollout_sampler", "torch")))
         return ImpalaTrainer(venv, policy, imp_cfg, device=device)
     ppo_cfg = PPOConfig(

@@ -37,9 +37,14 @@ the ``device`` trainer.
 ``device_torch_trunk``, the device learner with the same ``--head-step`` and
 the torch trunk, and the launch count is taken for both of them.
 
+``--optimizer-step fused`` gives the ``device`` trainer (and only it) the
+one-launch optimiser tail (ops/hip/learner_tail.hip); the launch count then
+also reports its ``lt_`` kernels, one per minibatch.
+
 Usage: python scripts/dqn_learner_bench.py [--envs 256] [--iters 10]
            [--warmup 2] [--prioritized] [--head-step {torch,fused}]
-           [--trunk-step {torch,fused}] [--count-launches] [--out FILE]
+           [--trunk-step {torch,fused}] [--optimizer-step {torch,fused}]
+           [--count-launches] [--out FILE]
 """
 import argparse
 import json
@@ -75,6 +80,9 @@ def main():
                     default="torch", help="the device learner's Q-head step")
     ap.add_argument("--trunk-step", choices=("torch", "fused"),
                     default="torch", help="the device learner's GNN trunk")
+    ap.add_argument("--optimizer-step", choices=("torch", "fused"),
+                    default="torch",
+                    help="the `device` trainer's optimiser tail")
     ap.add_argument("--sampler", choices=("torch", "device", "fused"),
                     default="torch",
                     help="DQNConfig.rollout_sampler of every trainer")
@@ -108,7 +116,8 @@ def main():
     num_actions = cfg["env_config"].get("max_partitions_per_op", 16) + 1
     steps = max(1, algo["train_batch_size"] // args.envs)
 
-    def trainer(learner, head_step="torch", trunk_step="torch"):
+    def trainer(learner, head_step="torch", trunk_step="torch",
+                optimizer_step="torch"):
         venv = EngineVectorEnv(env_fn, num_envs=args.envs, device=dev,
                                base_seed=0, spec=spec, proto_env=proto)
         torch.manual_seed(0)
@@ -122,7 +131,7 @@ def main():
             sgd_minibatch_size=algo["sgd_minibatch_size"],
             num_sgd_iter=algo["num_sgd_iter"], learner=learner,
             head_step=head_step, trunk_step=trunk_step,
-            rollout_sampler=args.sampler,
+            optimizer_step=optimizer_step, rollout_sampler=args.sampler,
             prioritized_replay=args.prioritized,
             prioritized_replay_alpha=algo["prioritized_replay_alpha"],
             prioritized_replay_beta=algo["prioritized_replay_beta"],
@@ -130,7 +139,8 @@ def main():
             device=dev)
 
     trainers = {"torch": trainer("torch"),
-                "device": trainer("device", args.head_step, args.trunk_step)}
+                "device": trainer("device", args.head_step, args.trunk_step,
+                                  args.optimizer_step)}
     if args.trunk_step == "fused":
         trainers["device_torch_trunk"] = trainer("device", args.head_step)
     elif args.head_step == "fused":
@@ -167,7 +177,8 @@ def main():
            "num_sgd_iter": algo["num_sgd_iter"], "n_step": algo["n_step"],
            "iters": args.iters, "warmup": args.warmup,
            "prioritized": args.prioritized, "head_step": args.head_step,
-           "trunk_step": args.trunk_step, "sampler": args.sampler}
+           "trunk_step": args.trunk_step,
+           "optimizer_step": args.optimizer_step, "sampler": args.sampler}
     for name in trainers:
         assert last[name]["learner"] == (0 if name == "torch" else 1)
         assert last[name].get("head_step", 0) == int(
@@ -175,6 +186,8 @@ def main():
             and args.head_step == "fused")
         assert last[name].get("trunk_step", 0) == int(
             name == "device" and args.trunk_step == "fused")
+        assert last[name].get("optimizer_step", 0) == int(
+            name == "device" and args.optimizer_step == "fused")
         assert last[name]["total_loss"] > 0, "the timed updates must train"
         out[name] = {"update_time_s": summary(update[name]),
                      "rollout_time_s": summary(rollout[name]),
@@ -234,6 +247,7 @@ def main():
             "dqn_kernels": sum(n.startswith("dqn_") for n in names),
             "dqn_hs_kernels": sum(n.startswith("dqn_hs_") for n in names),
             "gt_kernels": sum(n.startswith("gt_") for n in names),
+            "lt_kernels": sum(n.startswith("lt_") for n in names),
             # less the ingest (and, prioritized, the per_ingest) launch
             "per_minibatch": (len(names) - (2 if args.prioritized else 1))
             / algo["num_sgd_iter"]}

@@ -2,7 +2,10 @@
 """IMPALA (V-trace) / PG training session on the GPU-resident env engine —
 demonstrates the non-PPO algorithms end-to-end on the flagship stack.
 Env: ALGO=impala|pg ITERS=N OUT=dir LEARNER=torch|device and, for the device
-learner, HEAD_STEP=torch|fused TRUNK_STEP=torch|fused (IMPALA only); EVAL=0 skips the greedy evaluation after training."""
+learner, HEAD_STEP=torch|fused TRUNK_STEP=torch|fused
+OPTIMIZER_STEP=torch|fused (IMPALA only); COUNT_LAUNCHES=1 also profiles one
+more update and reports the kernels it launched; EVAL=0 skips the greedy
+evaluation after training."""
 import json
 import os
 import sys
@@ -23,6 +26,7 @@ OUT = os.environ.get("OUT", f"gpurun_out/{ALGO}_session")
 LEARNER = os.environ.get("LEARNER", "torch")
 HEAD_STEP = os.environ.get("HEAD_STEP", "torch")
 TRUNK_STEP = os.environ.get("TRUNK_STEP", "torch")
+OPTIMIZER_STEP = os.environ.get("OPTIMIZER_STEP", "torch")
 
 
 def main():
@@ -40,7 +44,9 @@ def main():
                            ImpalaConfig(train_batch_size=4096,
                                         learner=LEARNER,
                                         head_step=HEAD_STEP,
-                                        trunk_step=TRUNK_STEP), device=dev)
+                                        trunk_step=TRUNK_STEP,
+                                        optimizer_step=OPTIMIZER_STEP),
+                           device=dev)
     log = []
     t0 = time.time()
     for i in range(ITERS):
@@ -60,9 +66,27 @@ def main():
           f"{tr.total_env_steps/dt:,.0f} steps/s")
     # how an iteration divides (the first one carries warm-up, leave it out)
     tail = log[1:] or log
+    launches = None
+    if os.environ.get("COUNT_LAUNCHES", "0") == "1":
+        from torch.autograd import DeviceType
+        from torch.profiler import ProfilerActivity, profile
+        data = tr.collect_rollout(16)
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU,
+                                 ProfilerActivity.CUDA]) as prof:
+            tr.update(data)
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events()
+                 if e.device_type == DeviceType.CUDA
+                 and not e.name.lower().startswith(("memcpy", "memset"))]
+        launches = {"kernels": len(names),
+                    "lt_kernels": sum(n.startswith("lt_") for n in names)}
     print(json.dumps({
         "algo": ALGO, "learner": LEARNER, "head_step": HEAD_STEP,
-        "trunk_step": TRUNK_STEP, "iters": ITERS,
+        "trunk_step": TRUNK_STEP, "optimizer_step": OPTIMIZER_STEP,
+        "update_launches": launches,
+        "update_ms_all": [1e3 * r["update_time_s"] for r in tail],
+        "iters": ITERS,
         "env_steps_per_s": tr.total_env_steps / dt,
         "rollout_ms": 1e3 * sum(r["rollout_time_s"] for r in tail) / len(tail),
         "update_ms": 1e3 * sum(r["update_time_s"] for r in tail) / len(tail),
